@@ -11,7 +11,15 @@ forward (dropout on) + GQA loss with semantic prior + backward + gradient all-re
 zero-grad.  Weak scaling: 256 samples per GPU.  Rank 0 prints ONE JSON line.  `--workload c3|c4|c5` runs the other
 BASELINE configs through the same code (their lines are committed under profiles/, they are not the headline).
 
-Extra objects on the line:
+A plain run sets up, warms up, times `--steps` steps and prints the line (`value`, `ms_per_step`); `--dump-outputs DIR`
+additionally writes what the last timed step left behind (loss, batch score, a fixed seeded sample of the parameters and
+of both AdamW moments) as float32 DIR/<name>.npy, so that two builds can be compared output for output.
+
+`--full` adds the measurements beside the headline (otherwise null on the line):
+  extras        forward+backward only, PCIe-inclusive (batches from pinned host memory) and, for N > 1, the reference's
+                global-256 batch semantics -- each timed in a run of its own after the timed steps.
+
+Extra objects on the line (`--full` only):
   roofline      the dominant kernel (the 3-pass bf16 MFMA GEMM of the forward): algorithmic FLOP (2*M*N*K per launch,
                 NOT x3 for the split passes) / duration measured live with HIP events on the launch stream inside the
                 timed region (the native stack brackets every 11th GEMM launch with caller-owned events), against the
@@ -194,6 +202,30 @@ def cpu_baseline(seconds_budget=40.0):
                        % (n_full, n_fb))
 
 
+DUMP_SAMPLE_PER_TENSOR = 16384
+
+
+def dump_outputs(out_dir, loss, score, opt):
+    """What the caller of the training step holds after the last timed step, as float32 .npy: the loss and batch score it
+    returned, and the state it left -- parameters and both AdamW moments, sampled at the same fixed seeded positions of
+    every parameter tensor (all of a tensor up to DUMP_SAMPLE_PER_TENSOR elements): 1.4 M elements per array for c2,
+    3.2 M for c4, 16 MB / 36 MB in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    rs = np.random.RandomState(20240601)
+    a = opt.arena
+    idx = []
+    for (_, p, _, _), off in zip(a.groups, a.offsets):
+        n = p.numel()
+        sel = np.arange(n) if n <= DUMP_SAMPLE_PER_TENSOR else np.unique(rs.randint(0, n, size=DUMP_SAMPLE_PER_TENSOR))
+        idx.append(off + sel)
+    idx = torch.from_numpy(np.concatenate(idx)).to(a.param.device)
+    arrays = {"loss": loss.detach().reshape(1), "batch_score": score.detach().reshape(1),
+              "param_sample": a.param[idx], "adam_exp_avg_sample": opt.exp_avg[idx],
+              "adam_exp_avg_sq_sample": opt.exp_avg_sq[idx]}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -209,6 +241,10 @@ def main():
                     "(forward+backward only, PCIe-inclusive, reference batch semantics): used under the profiler")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse "
                     "the multi-rank logic on a single GPU)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the live GEMM "
+                    "roofline (event pairs inside the timed region), the extras and the CPU oracle baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as "
+                    "float32 DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -314,7 +350,7 @@ def main():
     batch = batches[0]
     step_no = [0]
     crit = torch.nn.CrossEntropyLoss()
-    timer = GemmTimer(model.engine.stack) if os.environ.get("BENCH_NO_GEMM_TIMER", "0") != "1" else None
+    timer = GemmTimer(model.engine.stack) if args.full and os.environ.get("BENCH_NO_GEMM_TIMER", "0") != "1" else None
 
     host = [0.0, 0.0, 0.0]  # host-side enqueue seconds (forward, backward, optimizer) -- diagnostics only
 
@@ -331,7 +367,7 @@ def main():
         host[0] += c1 - c0
         host[1] += c2 - c1
         host[2] += c3 - c2
-        return loss
+        return loss, score
 
     if os.environ.get("BENCH_MAIN_HIGH", "0") == "1":  # A/B: the training step on a high-priority stream
         hp = torch.cuda.Stream(device=dev, priority=-1)
@@ -348,7 +384,7 @@ def main():
     host[:] = [0.0, 0.0, 0.0]
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, score = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -361,6 +397,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     final_loss = float(loss.detach())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, score, opt)
     # multi-GPU observability (read after the timed region): backend, world size, how long the main stream waited for the
     # gradient exchange per step (HIP events around the wait loop of FusedAdamW.step) and the bytes each rank exchanged
     dist_obs = None
@@ -391,7 +429,7 @@ def main():
         loss_, _ = task_utils.ForwardModelsTrain(config, TASK_CFG, dev, "TASK15", batch, model, crit)
         loss_.backward()
         opt.discard_grads()  # no optimizer step: drop the gradients instead of accumulating them over iterations
-    n_extra = 0 if args.no_extras else max(3, args.steps // 2)
+    n_extra = max(3, args.steps // 2) if args.full and not args.no_extras else 0
     fb_rate = None
     if n_extra:
         if world > 1:
@@ -502,7 +540,7 @@ def main():
                                                               "gradient carry state)" % (args.batch * 20)}
         line["dist"] = dist_obs
         print("[bench] gpu part done: %.1f samples/s, %.2f ms/step" % (value, 1e3 * elapsed / args.steps), file=sys.stderr, flush=True)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             del model, opt
             torch.cuda.empty_cache()
             line["cpu_baseline"] = cpu_baseline()

@@ -2,7 +2,7 @@
 # Prints ms / step and the live roofline fractions (forward 3-pass GEMM, fused attention op, backward dX GEMMs) per config.
 for cfg in ${AB_CONFIGS:-"X=0"}; do
   echo "== $cfg"
-  env $(echo $cfg | tr ';' ' ') timeout -k 10 300 python bench.py --steps ${AB_STEPS:-20} --warmup 5 --no-cpu-baseline --no-extras ${AB_ARGS:-} 2>/tmp/ab_err.txt | python3 -c "
+  env $(echo $cfg | tr ';' ' ') timeout -k 10 300 python bench.py --full --steps ${AB_STEPS:-20} --warmup 5 --no-cpu-baseline --no-extras ${AB_ARGS:-} 2>/tmp/ab_err.txt | python3 -c "
 import json, sys
 try:
     d = json.loads(sys.stdin.read().strip().split('\n')[-1])
