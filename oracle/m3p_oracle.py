@@ -15,7 +15,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .uc2_oracle import _Classifier, gelu_erf
+from .uc2_oracle import _Classifier, dropout, gelu_erf
 
 N_MAX_POSITIONS = 514  # m3p_transformer.py
 
@@ -31,8 +31,8 @@ class _ImageEmbeddings(nn.Module):
         self.p = p
 
     def forward(self, feat, loc):
-        return F.dropout(self.LayerNorm(self.image_embeddings(feat) + self.image_location_embeddings(loc)), self.p,
-                         self.training)
+        return dropout(self, self.LayerNorm(self.image_embeddings(feat) + self.image_location_embeddings(loc)), self.p,
+                       "emb_image")
 
 
 class _MHA(nn.Module):
@@ -99,7 +99,7 @@ class OracleM3PForVLTasks(nn.Module):
         mask = (torch.arange(S)[None, :] < lens[:, None])                               # get_masks :59-78
         mf = mask.unsqueeze(-1).to(t.dtype)
         t = t * mf                                                                      # :937
-        t = F.dropout(e.layer_norm_emb(t), c.dropout, self.training)
+        t = dropout(self, e.layer_norm_emb(t), c.dropout, "emb_joint")
         for i in range(c.n_layers):
             a = e.attentions[i]
 
@@ -109,12 +109,12 @@ class OracleM3PForVLTasks(nn.Module):
             q = shape(a.q_lin(t)) / math.sqrt(dh)                                       # :197
             scores = torch.matmul(q, shape(a.k_lin(t)).transpose(2, 3))
             scores = scores.masked_fill((mask == 0)[:, None, None, :], -float("inf"))   # :199-200
-            w = F.dropout(F.softmax(scores.float(), dim=-1), c.attention_dropout, self.training)
+            w = dropout(self, F.softmax(scores.float(), dim=-1), c.attention_dropout, "attn_probs", i)
             ctx = torch.matmul(w, shape(a.v_lin(t))).transpose(1, 2).contiguous().view(B, S, c.emb_dim)
-            t = e.layer_norm1[i](t + F.dropout(a.out_lin(ctx), c.dropout, self.training))
+            t = e.layer_norm1[i](t + dropout(self, a.out_lin(ctx), c.dropout, "attn_out", i))
             f = e.ffns[i]
-            t = e.layer_norm2[i](t + F.dropout(f.lin2(gelu_erf(f.lin1(t))), c.dropout, self.training))
+            t = e.layer_norm2[i](t + dropout(self, f.lin2(gelu_erf(f.lin1(t))), c.dropout, "ffn_out", i))
             t = t * mf                                                                  # :955
         pooled = torch.tanh(self.bert.pooler.dense(t[:, 0]))                            # token 0 = first image region
-        pooled = F.dropout(pooled, self.p_pool, self.training)                          # encoders.py:1337
+        pooled = dropout(self, pooled, self.p_pool, "pooled")                            # encoders.py:1337
         return self.clfs_dict[task_id](pooled), None, None, None

@@ -43,6 +43,23 @@ class TFLayerNorm(nn.Module):
         return self.weight * ((x - u) / torch.sqrt(s + self.variance_epsilon)) + self.bias
 
 
+def dropout(module, x, p, site, layer=0):
+    """Every dropout of the oracles goes through here.  Without a mask provider (the default) it is F.dropout; with one
+    (set_mask_provider, test infrastructure) a training-mode module multiplies by ``provider(site, layer, shape)`` instead:
+    the keep-scales (0 or 1 / (1 - p)) the HIP path draws from its counter-based generators.  Sites: emb_text, emb_box
+    (M3P: emb_image, emb_joint), attn_probs, attn_out, ffn_out (per layer), pooled."""
+    provider = getattr(module, "mask_provider", None)
+    if provider is None or not module.training or p <= 0:
+        return F.dropout(x, p, module.training)
+    return x * provider(site, layer, tuple(x.shape)).to(dtype=x.dtype, device=x.device)
+
+
+def set_mask_provider(model, provider):
+    """Install (or with None remove) the mask provider on every module of an oracle model."""
+    for m in model.modules():
+        m.mask_provider = provider
+
+
 def roberta_position_ids(input_ids, padding_idx):
     """volta/embeddings.py:157-170 -- pos = cumsum(ids != pad) * (ids != pad) + pad."""
     mask = input_ids.ne(padding_idx).int()
@@ -74,12 +91,12 @@ class _Embeddings(nn.Module):
         pos = roberta_position_ids(token_ids, self.padding_idx)
         e = self.word_embeddings(token_ids) + self.position_embeddings(pos) \
             + self.new_token_type_embeddings(token_type_ids)
-        e = F.dropout(self.LayerNorm(e), self.p, self.training)
+        e = dropout(self, self.LayerNorm(e), self.p, "emb_text")
         img = self.image_layer_norm(self.image_embeddings(image_feat))
         loc = self.image_location_layer_norm(self.image_location_embeddings(image_loc))
         ones = torch.ones_like(image_feat[:, :, 0].long())
         v = self.v_LayerNorm(img + loc + self.image_token_type_embeddings(ones))
-        v = F.dropout(v, self.p, self.training)
+        v = dropout(self, v, self.p, "emb_box")
         return e, v
 
 
@@ -124,10 +141,10 @@ class _AttnSublayer(nn.Module):
 
         q, k, v = heads(a.query(x)), heads(a.key(x)), heads(a.value(x))
         scores = torch.matmul(q, k.transpose(-1, -2)) / math.sqrt(dh) + add_mask  # [B,nh,S,S]
-        probs = F.dropout(torch.softmax(scores, dim=-1), self.p_attn, self.training)
+        probs = dropout(self, torch.softmax(scores, dim=-1), self.p_attn, "attn_probs", self.layer_idx)
         ctx = torch.matmul(probs, v).permute(0, 2, 1, 3).reshape(B, S, H)
         o = self.attention_output
-        return o.LayerNorm(F.dropout(o.dense(ctx), self.p_hid, self.training) + x)
+        return o.LayerNorm(dropout(self, o.dense(ctx), self.p_hid, "attn_out", self.layer_idx) + x)
 
 
 class _Intermediate(nn.Module):
@@ -157,7 +174,7 @@ class _FFSublayer(nn.Module):
     def forward(self, x):
         h = gelu_erf(self.intermediate.dense(x))
         o = self.output
-        return o.LayerNorm(F.dropout(o.dense(h), self.p_hid, self.training) + x)
+        return o.LayerNorm(dropout(self, o.dense(h), self.p_hid, "ffn_out", self.layer_idx) + x)
 
 
 class _Encoder(nn.Module):
@@ -166,8 +183,9 @@ class _Encoder(nn.Module):
     def __init__(self, c, n_layers):
         super().__init__()
         subs = []
-        for _ in range(n_layers):
+        for l in range(n_layers):
             subs += [_AttnSublayer(c), _FFSublayer(c)]
+            subs[-2].layer_idx = subs[-1].layer_idx = l
         self.layer = nn.ModuleList(subs)
 
 
@@ -242,7 +260,7 @@ class OracleUC2ForVLTasks(nn.Module):
         for i, layer in enumerate(self.bert.encoder.layer):
             x = layer(x, add_mask) if i % 2 == 0 else layer(x)
         pooled = self.bert.t_pooler(x)                                 # token 0 is text (<s>)
-        pooled = F.dropout(pooled, self.p_pool, self.training)          # encoders.py:1238-1239
+        pooled = dropout(self, pooled, self.p_pool, "pooled")            # encoders.py:1238-1239
         logits = self.clfs_dict[task_id](pooled)                       # encoders.py:1254
         return logits, None, None, None
 
