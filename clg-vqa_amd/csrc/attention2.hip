@@ -72,6 +72,7 @@ struct Attn2Args {
   int ctx_rows;      // rows per sample of ctx / dctx (S, or 1 in the compact layout)
   float scale, p_drop, inv_keep;
   unsigned seed_lo, seed_hi, thr16;
+  float* probs;      // forward, EMIT instances only: [B, nh, S, S] fp32 (last: the offsets of the fields above are unchanged)
 };
 
 __device__ __forceinline__ f32x4 mfma(bf16x8 a, bf16x8 b, f32x4 c) {
@@ -211,7 +212,11 @@ template <int DH, int NTHR, int SPAD, int NM> struct StageBatch {
 #ifndef VL_ATTN_BWD_NW
 #define VL_ATTN_BWD_NW(NT) ((NT) >= 10 ? 8 : 4)
 #endif
-template <int NT, int DH, int NW>
+// EMIT (vl_attn2_fwd_probs) additionally stores the probabilities as they multiply V -- softmax of the masked, scaled
+// scores, times the dropout keep scale (the tensors the reference returns for visualisation, encoders.py:295-296, 310-311,
+// 344-355) -- to p.probs [B, nh, S, S] fp32: the same arithmetic in the same order, only stores are added.  A compile-time
+// flag: the plain instantiations keep their code and register budgets (tools/regs.sh).
+template <int NT, int DH, int NW, bool EMIT = false>
 __global__ __launch_bounds__(NW * 64, VL_ATTN_FWD_MINW(NT, NW)) void attn2_fwd_kernel(Attn2Args p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
   constexpr int Spad = NT * 16, NP = (NT + 1) / 2;  // key-tile pairs
@@ -309,6 +314,14 @@ __global__ __launch_bounds__(NW * 64, VL_ATTN_FWD_MINW(NT, NW)) void attn2_fwd_k
     const float inv = 1.0f / sum;
     if (g == 0 && q < S) p.lse[((long)b * p.nh + h) * S + q] = m + __logf(sum);
     const unsigned row = (unsigned)((b * p.nh + h) * S + q);
+    // EMIT: the stored value is the fp32 product e * (inv * keep), formed from opaque copies of e and inv.  Sharing the
+    // multiply with the P.V path would give it a second use, and the compiler then no longer contracts it into the
+    // subtraction of the (hi, lo) split below (x - hi as one fma on the exact product): ctx_lo would differ from the plain
+    // kernel's in the last bit.  The copies keep the P.V path the expression it is without the stores.
+    float inv_e = inv;
+    if constexpr (EMIT) asm volatile("" : "+v"(inv_e));
+    float* prow = nullptr;
+    if constexpr (EMIT) prow = p.probs + (long)row * S;
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       float k0 = 1.f, k1 = 1.f, k2 = 1.f, k3 = 1.f;
@@ -316,6 +329,25 @@ __global__ __launch_bounds__(NW * 64, VL_ATTN_FWD_MINW(NT, NW)) void attn2_fwd_k
         const unsigned b0 = drop_bits(p, row, (unsigned)(8 * t + 2 * g), Spad / 2);
         const unsigned b1 = drop_bits(p, row, (unsigned)(8 * t + 2 * g + 1), Spad / 2);
         k0 = keep_of(p, b0, 0); k1 = keep_of(p, b0, 1); k2 = keep_of(p, b1, 0); k3 = keep_of(p, b1, 1);
+      }
+      if constexpr (EMIT) {
+        // this lane's keys 16 t + 4 g .. + 3 of query q: one 16-byte store when rows are 16-byte aligned (S % 4 == 0: a
+        // group of four keys is then either all below S or all padding), else up to four 4-byte stores.  Padded keys
+        // (>= S) and queries (>= nq) are not written.
+        float e0 = sc[t][0], e1 = sc[t][1], e2 = sc[t][2], e3 = sc[t][3];
+        asm volatile("" : "+v"(e0), "+v"(e1), "+v"(e2), "+v"(e3));
+        const float4 pe = make_float4(e0 * (inv_e * k0), e1 * (inv_e * k1), e2 * (inv_e * k2), e3 * (inv_e * k3));
+        const int key0 = 16 * t + 4 * g;
+        if (q < p.nq) {
+          if ((S & 3) == 0) {
+            if (key0 < S) *reinterpret_cast<float4*>(prow + key0) = pe;
+          } else {
+            if (key0 < S) prow[key0] = pe.x;
+            if (key0 + 1 < S) prow[key0 + 1] = pe.y;
+            if (key0 + 2 < S) prow[key0 + 2] = pe.z;
+            if (key0 + 3 < S) prow[key0 + 3] = pe.w;
+          }
+        }
       }
       sc[t][0] *= inv * k0; sc[t][1] *= inv * k1; sc[t][2] *= inv * k2; sc[t][3] *= inv * k3;
     }
@@ -551,10 +583,14 @@ __global__ __launch_bounds__(NW * 64, VL_ATTN_BWD_MINW(NT, NW)) void attn2_bwd_k
 template <int NT, int DH, int NW>
 int launch_fwd(const Attn2Args& a, hipStream_t s) {
   const size_t lds = (size_t)NT * 16 * (4 * Geo<DH>::PITCH + 4);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn2_fwd_kernel<NT, DH, NW>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  const void* fn = a.probs ? reinterpret_cast<const void*>(&attn2_fwd_kernel<NT, DH, NW, true>)
+                           : reinterpret_cast<const void*>(&attn2_fwd_kernel<NT, DH, NW, false>);
+  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return vl_set_error(-3, "vl_attn2_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
-  hipLaunchKernelGGL((attn2_fwd_kernel<NT, DH, NW>), dim3(a.B * a.nh), dim3(NW * 64), lds, s, a);
+  if (a.probs)
+    hipLaunchKernelGGL((attn2_fwd_kernel<NT, DH, NW, true>), dim3(a.B * a.nh), dim3(NW * 64), lds, s, a);
+  else
+    hipLaunchKernelGGL((attn2_fwd_kernel<NT, DH, NW, false>), dim3(a.B * a.nh), dim3(NW * 64), lds, s, a);
   VL_CHECK_LAUNCH("vl_attn2_fwd");
   return 0;
 }
@@ -605,17 +641,36 @@ inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) 
 
 }  // namespace
 
+namespace {
+int attn2_fwd_impl(const char* fn, const void* qkv_hi, const void* qkv_lo, const float* addmask, void* ctx_hi, void* ctx_lo,
+                   float* lse, float* probs, int64_t B, int64_t S, int64_t nh, int64_t dh, int64_t nq, float p_drop,
+                   uint64_t seed, void* stream) {
+  Attn2Args a{};
+  if (int rc = fill_common(fn, a, B, S, nh, dh, nq, p_drop, seed)) return rc;
+  VL_CHECK_ARG(qkv_hi && qkv_lo && addmask && ctx_hi && ctx_lo && lse, "%s: null pointer", fn);
+  VL_CHECK_ARG(al16(qkv_hi) && al16(qkv_lo) && al16(ctx_hi) && al16(ctx_lo), "%s: pointers must be 16-byte aligned", fn);
+  VL_CHECK_ARG(!probs || al16(probs), "%s: probs must be 16-byte aligned", fn);
+  a.qkv_hi = (const bf16_raw*)qkv_hi; a.qkv_lo = (const bf16_raw*)qkv_lo; a.addmask = addmask;
+  a.ctx_hi = (bf16_raw*)ctx_hi; a.ctx_lo = (bf16_raw*)ctx_lo; a.lse = lse; a.probs = probs;
+  hipStream_t s = (hipStream_t)stream;
+  return dh == 64 ? dispatch_fwd<64>(a, s) : dispatch_fwd<32>(a, s);
+}
+}  // namespace
+
 extern "C" int vl_attn2_fwd(const void* qkv_hi, const void* qkv_lo, const float* addmask, void* ctx_hi, void* ctx_lo,
                             float* lse, int64_t B, int64_t S, int64_t nh, int64_t dh, int64_t nq, float p_drop,
                             uint64_t seed, void* stream) {
-  Attn2Args a{};
-  if (int rc = fill_common("vl_attn2_fwd", a, B, S, nh, dh, nq, p_drop, seed)) return rc;
-  VL_CHECK_ARG(qkv_hi && qkv_lo && addmask && ctx_hi && ctx_lo && lse, "vl_attn2_fwd: null pointer");
-  VL_CHECK_ARG(al16(qkv_hi) && al16(qkv_lo) && al16(ctx_hi) && al16(ctx_lo), "vl_attn2_fwd: pointers must be 16-byte aligned");
-  a.qkv_hi = (const bf16_raw*)qkv_hi; a.qkv_lo = (const bf16_raw*)qkv_lo; a.addmask = addmask;
-  a.ctx_hi = (bf16_raw*)ctx_hi; a.ctx_lo = (bf16_raw*)ctx_lo; a.lse = lse;
-  hipStream_t s = (hipStream_t)stream;
-  return dh == 64 ? dispatch_fwd<64>(a, s) : dispatch_fwd<32>(a, s);
+  return attn2_fwd_impl("vl_attn2_fwd", qkv_hi, qkv_lo, addmask, ctx_hi, ctx_lo, lse, nullptr, B, S, nh, dh, nq, p_drop, seed,
+                        stream);
+}
+
+// vl_attn2_fwd + the probabilities that multiply V (post-dropout; encoders.py:286-311, 343-359) to probs [B, nh, S, S] fp32,
+// rows [0, nq) of every (sample, head); probs == NULL: exactly vl_attn2_fwd
+extern "C" int vl_attn2_fwd_probs(const void* qkv_hi, const void* qkv_lo, const float* addmask, void* ctx_hi, void* ctx_lo,
+                                  float* lse, float* probs, int64_t B, int64_t S, int64_t nh, int64_t dh, int64_t nq,
+                                  float p_drop, uint64_t seed, void* stream) {
+  return attn2_fwd_impl("vl_attn2_fwd_probs", qkv_hi, qkv_lo, addmask, ctx_hi, ctx_lo, lse, probs, B, S, nh, dh, nq, p_drop,
+                        seed, stream);
 }
 
 extern "C" int vl_attn2_bwd(const void* qkv_hi, const float* addmask, const void* dctx16, const float* lse,

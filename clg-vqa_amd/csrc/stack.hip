@@ -98,6 +98,11 @@ bool fused_du(const int64_t* d, int64_t l) {  // bit 1: du + its column sums by 
   return (d[VL_ST_FUSE_IMAGES] & 2) && y[VL_LY_T_DU] && y[VL_LY_CS_DU] && fused_shape(d, l);
 }
 
+int tap_copy(float* dst, const float* src, int64_t n, void* stream) {
+  const hipError_t e = hipMemcpyAsync(dst, src, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : vl_set_error(-3, "vl_stack_fwd: tap copy: %s", hipGetErrorString(e));
+}
+
 int check_header(const char* fn, const int64_t* d) {
   VL_CHECK_ARG(d, "%s: null descriptor", fn);
   VL_CHECK_ARG(d[VL_ST_MAGIC] == VL_ST_MAGIC_VALUE, "%s: descriptor magic mismatch (built for another library version?)", fn);
@@ -144,6 +149,27 @@ extern "C" int vl_qkv_attention_fwd(const void* x_hi, const void* x_lo, const vo
   return vl_attn2_fwd(qkv_hi, qkv_lo, addmask, ctx_hi, ctx_lo, lse, B, S, nh, dh, nq, p_drop, seed, stream);
 }
 
+// The same op with the attention probabilities emitted (vl_attn2_fwd_probs; encoders.py:286-311, 343-359).  All arguments
+// are checked before the projection is launched.
+extern "C" int vl_qkv_attention_fwd_probs(const void* x_hi, const void* x_lo, const void* wqkv_hi, const void* wqkv_lo,
+                                          const float* bqkv, const float* addmask, void* qkv_hi, void* qkv_lo, void* ctx_hi,
+                                          void* ctx_lo, float* lse, float* probs, int64_t B, int64_t S, int64_t nh, int64_t dh,
+                                          int64_t nq, float p_drop, uint64_t seed, void* stream) {
+  VL_CHECK_ARG(dh == 64 || dh == 32, "vl_qkv_attention_fwd_probs: head dim must be 64 or 32 (got %lld)", (long long)dh);
+  VL_CHECK_ARG(S >= 1 && S <= 160, "vl_qkv_attention_fwd_probs: sequence length T+V must be in [1,160] (got %lld)", (long long)S);
+  VL_CHECK_ARG(B >= 1 && nh >= 1 && B * nh < (1LL << 30) && B * nh * S < (1LL << 31), "vl_qkv_attention_fwd_probs: bad B=%lld nh=%lld",
+               (long long)B, (long long)nh);
+  VL_CHECK_ARG(nq >= 1 && nq <= S, "vl_qkv_attention_fwd_probs: nq must be in [1, S] (got %lld)", (long long)nq);
+  VL_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "vl_qkv_attention_fwd_probs: dropout p must be in [0,1)");
+  VL_CHECK_ARG(x_hi && x_lo && wqkv_hi && wqkv_lo && bqkv && addmask && qkv_hi && qkv_lo && ctx_hi && ctx_lo && lse,
+               "vl_qkv_attention_fwd_probs: null pointer");
+  VL_CHECK_ARG((reinterpret_cast<uintptr_t>(probs) & 15u) == 0, "vl_qkv_attention_fwd_probs: probs must be 16-byte aligned");
+  const int64_t H = nh * dh, M = B * S;
+  VL_TRY(vl_gemm_nt(x_hi, x_lo, H, wqkv_hi, wqkv_lo, H, M, 3 * H, H, 3, VL_EPI_SPLIT, bqkv, nullptr, nullptr, 0, qkv_hi, qkv_lo,
+                    nullptr, 3 * H, stream));
+  return vl_attn2_fwd_probs(qkv_hi, qkv_lo, addmask, ctx_hi, ctx_lo, lse, probs, B, S, nh, dh, nq, p_drop, seed, stream);
+}
+
 // Backward of the same op w.r.t. its input: dctx16 -> dqkv16 (attention backward) -> dx32 = dqkv . W_qkv (+ resid32).
 // (The weight / bias gradients of the projection are products over the batch rows: vl_transpose_blocked + vl_dw_grouped.)
 extern "C" int vl_qkv_attention_bwd(const void* qkv_hi, const float* addmask, const void* dctx16, const float* lse,
@@ -169,6 +195,12 @@ extern "C" int vl_stack_fwd(const int64_t* d, int64_t layer_begin, int64_t layer
   const GemmCtx gc{prof, ptr<float>(d[VL_ST_SMALL_WS]), d[VL_ST_SMALL_WS_FLOATS], d[VL_ST_DX_TILE], d[VL_ST_GEMM_PERSIST]};
   hipStream_t ss = stream_side ? (hipStream_t)stream_side : (hipStream_t)stream;
   hipEvent_t fork = ptr<ihipEvent_t>(d[VL_ST_EV_FORK]);
+  if (d[VL_ST_POOLED_ONLY] != 0 && layer_end == L) {  // before anything is enqueued
+    const int64_t* y = d + VL_ST_FIELDS + (L - 1) * VL_LY_FIELDS;
+    VL_CHECK_ARG(!y[VL_LY_TAP_PROBS] && !y[VL_LY_TAP_X1] && !y[VL_LY_TAP_OUT],
+                 "vl_stack_fwd: layer %lld runs in the pooled-row mode (VL_ST_POOLED_ONLY): its rows are never computed, so it "
+                 "cannot be tapped (VL_LY_TAP_*)", (long long)(L - 1));
+  }
   for (int64_t l = layer_begin; l < layer_end; ++l) {
     const int64_t* y = d + VL_ST_FIELDS + l * VL_LY_FIELDS;
     const int s3 = (int)(16 * l + 3);
@@ -185,6 +217,13 @@ extern "C" int vl_stack_fwd(const int64_t* d, int64_t layer_begin, int64_t layer
     // VL_PROF_TAG_QKV_ATTN: projection + core FLOPs against the interval around both launches)
     {
       int64_t* pair = prof_begin(prof, stream);
+      if (y[VL_LY_TAP_PROBS])  // tap: the emitting variant of the attention kernel (same ctx / lse)
+        VL_TRY(vl_qkv_attention_fwd_probs(ptr<void>(y[VL_LY_X_HI]), ptr<void>(y[VL_LY_X_LO]), ptr<void>(y[VL_LY_WQKV_HI]),
+                                          ptr<void>(y[VL_LY_WQKV_LO]), ptr<const float>(y[VL_LY_BQKV]), addmask,
+                                          ptr<void>(y[VL_LY_QKV_HI]), ptr<void>(y[VL_LY_QKV_LO]), ptr<void>(y[VL_LY_CTX_HI]),
+                                          ptr<void>(y[VL_LY_CTX_LO]), ptr<float>(y[VL_LY_LSE]), ptr<float>(y[VL_LY_TAP_PROBS]), B, S,
+                                          nh, H / nh, nq, p_att, seed_of(d[VL_ST_SEED0], s3), stream));
+      else
       VL_TRY(vl_qkv_attention_fwd(ptr<void>(y[VL_LY_X_HI]), ptr<void>(y[VL_LY_X_LO]), ptr<void>(y[VL_LY_WQKV_HI]),
                                   ptr<void>(y[VL_LY_WQKV_LO]), ptr<const float>(y[VL_LY_BQKV]), addmask, ptr<void>(y[VL_LY_QKV_HI]),
                                   ptr<void>(y[VL_LY_QKV_LO]), ptr<void>(y[VL_LY_CTX_HI]), ptr<void>(y[VL_LY_CTX_LO]),
@@ -209,8 +248,9 @@ extern "C" int vl_stack_fwd(const int64_t* d, int64_t layer_begin, int64_t layer
                             rr1 ? yp[VL_LY_LN2_B] : 0, d[VL_ST_ROW_POST]};
     VL_TRY(vl_ln_fwd_rr(ptr<float>(y[VL_LY_Z1]), rr1 ? nullptr : ptr<const float>(y[VL_LY_X32]), rr1 ? rl1 : nullptr, nullptr, 1,
                         nullptr, nullptr, ptr<const float>(y[VL_LY_LN1_G]), ptr<const float>(y[VL_LY_LN1_B]), eps,
-                        RR ? nullptr : ptr<float>(y[VL_LY_X1_32]), ptr<void>(y[VL_LY_X1_HI]), ptr<void>(y[VL_LY_X1_LO]), ptr<float>(y[VL_LY_MEAN1]), ptr<float>(y[VL_LY_RSTD1]),
+                        RR ? ptr<float>(y[VL_LY_TAP_X1]) : ptr<float>(y[VL_LY_X1_32]), ptr<void>(y[VL_LY_X1_HI]), ptr<void>(y[VL_LY_X1_LO]), ptr<float>(y[VL_LY_MEAN1]), ptr<float>(y[VL_LY_RSTD1]),
                         R, H, R, 0, 0, p_hid, 0.f, seed_of(d[VL_ST_SEED0], s3 + 1), os, os, stream));
+    if (!RR && y[VL_LY_TAP_X1]) VL_TRY(tap_copy(ptr<float>(y[VL_LY_TAP_X1]), ptr<const float>(y[VL_LY_X1_32]), M * H, stream));
     const GemmImage him{ptr<void>(y[VL_LY_T_H]), I, nullptr, nullptr};
     VL_TRY(gemm(gc, ptr<void>(y[VL_LY_X1_HI]), ptr<void>(y[VL_LY_X1_LO]), H, ptr<void>(y[VL_LY_W1_HI]), ptr<void>(y[VL_LY_W1_LO]), H,
                 R, I, H, 3, VL_EPI_GELU_SPLIT, ptr<const float>(y[VL_LY_B1]), nullptr, nullptr, 0, ptr<void>(y[VL_LY_H_HI]),
@@ -221,9 +261,12 @@ extern "C" int vl_stack_fwd(const int64_t* d, int64_t layer_begin, int64_t layer
     const int64_t rl2[6] = {y[VL_LY_Z1], y[VL_LY_MEAN1], y[VL_LY_RSTD1], y[VL_LY_LN1_G], y[VL_LY_LN1_B], 0};
     VL_TRY(vl_ln_fwd_rr(ptr<float>(y[VL_LY_Z2]), RR ? nullptr : ptr<const float>(y[VL_LY_X1_32]), RR ? rl2 : nullptr, nullptr, 1,
                         nullptr, row_post, ptr<const float>(y[VL_LY_LN2_G]), ptr<const float>(y[VL_LY_LN2_B]), eps,
-                        (!RR || l == layer_end - 1) ? ptr<float>(y[VL_LY_OUT32]) : nullptr,
+                        (!RR || l == layer_end - 1) ? ptr<float>(y[VL_LY_OUT32]) : ptr<float>(y[VL_LY_TAP_OUT]),
                         ptr<void>(y[VL_LY_OUT_HI]), ptr<void>(y[VL_LY_OUT_LO]), ptr<float>(y[VL_LY_MEAN2]), ptr<float>(y[VL_LY_RSTD2]),
                         R, H, R, 0, 0, p_hid, 0.f, seed_of(d[VL_ST_SEED0], s3 + 2), os, 1, stream));
+    // (where the LayerNorm wrote OUT32 for the caller -- the last layer of the call -- the tap is a copy of it)
+    if ((!RR || l == layer_end - 1) && y[VL_LY_TAP_OUT])
+      VL_TRY(tap_copy(ptr<float>(y[VL_LY_TAP_OUT]), ptr<const float>(y[VL_LY_OUT32]), M * H, stream));
   }
   // training: the K-major images of the layers' X operands {layer input, attention context, LayerNorm-1 output, GELU
   // output} for the weight-gradient GEMMs of backward.  Those of the top layers (all but the bottom VL_ST_TR_BWD_LAYERS)

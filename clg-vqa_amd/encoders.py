@@ -358,19 +358,25 @@ class BertForVLTasks(PreTrainedModel):
 
     def forward(self, input_txt, input_imgs, image_loc, task_id, token_type_ids=None, attention_mask=None,
                 image_attention_mask=None, output_all_encoded_layers=False, output_all_attention_masks=False):
-        if output_all_encoded_layers or output_all_attention_masks:
-            raise NotImplementedError("clg_vqa_amd: per-layer outputs / attention maps are not materialised by the "
-                                      "fused trunk")
         if attention_mask is None:
             attention_mask = torch.ones_like(input_txt)
         if token_type_ids is None:
             token_type_ids = torch.zeros_like(input_txt)
         if image_attention_mask is None:
             image_attention_mask = torch.ones(input_imgs.size(0), input_imgs.size(1)).type_as(input_txt)
+        # per-layer outputs (encoders.py:848-892, 1256-1258): taps of the native stack, returned detached.  Attention data
+        # only exists when config.visualization is set (encoders.py:343-357): otherwise the reference returns None per
+        # sub-layer and no probability tap is switched on.
+        want_maps = bool(output_all_attention_masks and getattr(self.config, "visualization", False))
+        taps = dict(hidden=bool(output_all_encoded_layers), probs=want_maps) if output_all_encoded_layers or want_maps else None
         params = self._engine.param_list()
         self._engine.grad_mode = torch.is_grad_enabled()
-        x = UC2TrunkFunction.apply(self._engine, self.training, input_txt, input_imgs, image_loc, token_type_ids,
-                                   attention_mask, image_attention_mask, *params)
+        self._engine.tap_request = taps
+        try:
+            x = UC2TrunkFunction.apply(self._engine, self.training, input_txt, input_imgs, image_loc, token_type_ids,
+                                       attention_mask, image_attention_mask, *params)
+        finally:
+            self._engine.tap_request = None  # (a call that failed before the engine took the request must not leave it behind)
         if self._engine.chunks_pending:  # a pipelined optimizer update: the heads' parameters are its last chunk
             self._engine.wait_chunk(self._engine.n_chunks() - 1)
             self._engine.chunks_pending = False
@@ -382,7 +388,39 @@ class BertForVLTasks(PreTrainedModel):
             pooled_output_t = self.bert.t_pooler(x)
             pooled_output = self.dropout(pooled_output_t)  # fusion_method == "text" (encoders.py:1238-1239)
             vil_prediction = self.clfs_dict[task_id](pooled_output)
-        return vil_prediction, None, None, ([None], [None])
+        all_attention_mask = ([None], [None])
+        if output_all_attention_masks:
+            all_attention_mask = self._attention_data(taps if want_maps else None, input_txt.size(1))
+        if output_all_encoded_layers:
+            T = input_txt.size(1)
+            hs = [taps["embed"]]
+            for x1, out in zip(taps["x1"], taps["out"]):
+                hs += [x1, out]
+            return (vil_prediction, None, None, all_attention_mask, [h[:, :T] for h in hs], [h[:, T:] for h in hs])
+        return vil_prediction, None, None, all_attention_mask
+
+    def _attention_data(self, taps, T):
+        """(all_attention_mask_t, all_attention_mask_v) of BertEncoder.forward (encoders.py:863-881): [None], then one entry
+        per sub-layer -- None for feed-forward sub-layers and, without config.visualization (`taps` None), for attention
+        sub-layers too; else the dicts of encoders.py:343-355 cut out of the single-stream P [B, nh, S, S] (S = T + V) and
+        of the bias-added projections Q | K = hi + lo of the split the projection's epilogue wrote (exact in fp32)."""
+        list_t, list_v = [None], [None]
+        nh = self.config.num_attention_heads
+        for l in range(len(self.bert.encoder.layer) // 2):
+            ent_t = ent_v = None
+            if taps is not None:
+                P = taps["probs"][l]
+                hi, lo = taps["qkv"][l]
+                B, S, H = P.size(0), P.size(2), hi.size(1) // 3
+                qk = (hi[:, :2 * H].float() + lo[:, :2 * H].float()).view(B, S, 2, nh, H // nh).permute(2, 0, 3, 1, 4)
+                q, k = qk[0], qk[1]  # [B, nh, S, dh]
+                ent_t = dict(intra_attn=P[:, :, :T, :T], inter_attn=P[:, :, :T, T:], queries=q[:, :, :T], keys=k[:, :, :T])
+                ent_v = dict(intra_attn=P[:, :, T:, T:], inter_attn=P[:, :, T:, :T], queries=q[:, :, T:], keys=k[:, :, T:])
+            list_t += [ent_t, None]
+            list_v += [ent_v, None]
+        if taps is not None:
+            taps.pop("qkv")  # (the training arena's own buffers, or this call's per-layer copies: not part of the result)
+        return list_t, list_v
 
     def _task_head(self, task_id):
         heads = self.__dict__.setdefault("_vl_heads", {})

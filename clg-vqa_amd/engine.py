@@ -366,9 +366,12 @@ class LayerStack(object):
                      w1=PreparedWeight([sp.w1], device), w2=PreparedWeight([sp.w2], device)) for sp in self.specs]
 
     # ---- buffers + descriptor -------------------------------------------------------------------------------------
-    def arena(self, B, S, device, need_grad):
+    def arena(self, B, S, device, need_grad, pooled=None):
+        """`pooled`: whether the call runs the last layer in the pooled-row mode (None = ``self.pooled_only``; a tapped
+        call runs it dense)."""
+        pooled = self.pooled_only if pooled is None else pooled
         # K-major operand images are only needed when the weight-gradient GEMM cannot read the row-major activations
-        rowmajor = int(self.dw_rowmajor) == 3 and (B * S) % 64 == 0 and (not self.pooled_only or B % 64 == 0)
+        rowmajor = int(self.dw_rowmajor) == 3 and (B * S) % 64 == 0 and (not pooled or B % 64 == 0)
         key = (B, S, str(device), need_grad, rowmajor)
         lst = self._arenas.setdefault(key, [])
         for a in lst:
@@ -451,13 +454,49 @@ class LayerStack(object):
         """Where the embeddings write the stack's input: (x32, x_hi, x_lo) of layer 0."""
         return ar.x32[0], ar.x_hi[0], ar.x_lo[0]
 
-    def forward(self, ar, pw_layers, p_hid, p_att, seed0, row_post=None):
+    def _tap(self, d, ar, taps):
+        """Per-layer taps of one call (VL_LY_TAP_*): fresh tensors that belong to the caller -- one set per layer, never
+        shared between layers, also in inference -- returned through `taps` ("x1" / "out": L x [B, S, H] fp32 outputs of
+        the attention / feed-forward sub-layers; "probs": L x [B, nh, S, S] fp32; "qkv": L x (hi, lo) [B*S, 3H] bf16).
+        Works on a COPY of the cached descriptor, which therefore never carries a tap pointer: the next ordinary call
+        gets the ordinary descriptor back.  An inference arena shares one Q|K|V buffer between all layers, so a call
+        that wants the queries / keys gives every layer a Q|K|V buffer of its own for that call (no copy kernel between
+        layers; 4 * B*S * 3H bytes per layer until the caller has read them)."""
+        d = d.copy()
+        L, B, S, H, nh = len(self.specs), ar.B, ar.S, self.H, self.nh
+        dev = ar.x32.device
+        F, LF = VL["VL_ST_FIELDS"], VL["VL_LY_FIELDS"]
+        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
+        if taps.get("hidden"):
+            taps["x1"], taps["out"] = [f32(B, S, H) for _ in range(L)], [f32(B, S, H) for _ in range(L)]
+        if taps.get("probs"):
+            taps["probs"] = [f32(B, nh, S, S) for _ in range(L)]
+            if ar.need_grad:  # per layer already (backward reads them)
+                taps["qkv"] = [(ar.qkv_hi[l], ar.qkv_lo[l]) for l in range(L)]
+            else:
+                taps["qkv"] = [(torch.empty(B * S, 3 * H, dtype=BF16, device=dev), torch.empty(B * S, 3 * H, dtype=BF16, device=dev))
+                               for _ in range(L)]
+        for l in range(L):
+            y = F + l * LF
+            if taps.get("hidden"):
+                d[y + VL["VL_LY_TAP_X1"]], d[y + VL["VL_LY_TAP_OUT"]] = taps["x1"][l].data_ptr(), taps["out"][l].data_ptr()
+            if taps.get("probs"):
+                d[y + VL["VL_LY_TAP_PROBS"]] = taps["probs"][l].data_ptr()
+                d[y + VL["VL_LY_QKV_HI"]], d[y + VL["VL_LY_QKV_LO"]] = (t.data_ptr() for t in taps["qkv"][l])
+        return d
+
+    def forward(self, ar, pw_layers, p_hid, p_att, seed0, row_post=None, taps=None):
+        """`taps`: None, or a dict {"hidden": bool, "probs": bool} that asks for the per-layer outputs of this call and
+        receives them (_tap); such a call runs the last layer dense."""
+        pooled = self.pooled_only and taps is None
         d = self._descriptor(ar, pw_layers)
+        if taps is not None:
+            d = self._tap(d, ar, taps)
         d[VL["VL_ST_P_HID"]], d[VL["VL_ST_P_ATT"]] = _f32_bits(p_hid), _f32_bits(p_att)
         d[VL["VL_ST_SEED0"]] = seed0
         d[VL["VL_ST_ROW_POST"]] = 0 if row_post is None else ar.row_post.data_ptr()
         d[VL["VL_ST_PROF"]] = 0 if self.prof is None else self.prof.ctypes.data
-        d[VL["VL_ST_POOLED_ONLY"]] = 1 if self.pooled_only else 0
+        d[VL["VL_ST_POOLED_ONLY"]] = 1 if pooled else 0
         d[VL["VL_ST_TR_BLOCKS_FWD"]], d[VL["VL_ST_TR_BLOCKS_BWD"]] = self.tr_blocks
         d[VL["VL_ST_TR_BWD_LAYERS"]] = len(self.specs) - 1 if self.tr_bwd_layers is None else self.tr_bwd_layers
         d[VL["VL_ST_FUSE_IMAGES"]] = self.fuse_images
@@ -491,10 +530,10 @@ class LayerStack(object):
         L = len(self.specs)
         if ar.need_grad:
             ar.in_flight = True
-        ar.pooled = self.pooled_only
+        ar.pooled = pooled
         out = ar.x32[L % 2]
         H = self.H
-        return out[:ar.B].view(ar.B, 1, H) if self.pooled_only else out.view(ar.B, ar.S, H)
+        return out[:ar.B].view(ar.B, 1, H) if pooled else out.view(ar.B, ar.S, H)
 
     def backward(self, ar, pw_layers, dy, p_hid, p_att, seed0, row_post=None):
         """dy [M,H] fp32 = dL/d(stack output).  Returns (dL/d(stack input), per-layer grads in LayerSpec.params order:
@@ -588,6 +627,7 @@ class EngineBase(object):
         self.grad_mode = True  # torch.is_grad_enabled() at the model's call site (set by the module's forward)
         self._seed0 = 0
         self._last_arena = None
+        self.tap_request = None  # set by the module's forward for ONE call: {"hidden": bool, "probs": bool} (LayerStack._tap)
         # optimizer update under the next forward (FusedAdamW.pipeline_update): the update + weight preparation of chunk c
         # (0 = embeddings, 1 + l = layer l, last = task heads) runs on `update_stream`; the forward waits for chunk_events[c]
         self.supports_update_pipeline = False
@@ -794,7 +834,10 @@ class UC2Engine(EngineBase):
         tmask = tmask.contiguous().to(torch.int64); imask = imask.contiguous().to(torch.int64)
         feats2 = feats.contiguous().view(BV, F)
         locs2 = locs.contiguous().view(BV, L)
-        ar = self.stack.arena(B, S, dev, need_grad)
+        # per-layer outputs asked for by the module's forward (output_all_encoded_layers / output_all_attention_masks):
+        # a request holds for one call and is filled in place, the engine keeps no reference to the tensors
+        taps, self.tap_request = self.tap_request, None
+        ar = self.stack.arena(B, S, dev, need_grad, pooled=self.stack.pooled_only and taps is None)
         self._last_arena = ar
         sv = dict(B=B, T=T, V=V, F=F, L=L, S=S, p_hid=p_hid, p_att=p_att, seed=seed, seed0=seed0, ids=ids, seg=seg,
                   locs=locs2, pw=pw, arena=ar)
@@ -839,7 +882,9 @@ class UC2Engine(EngineBase):
                    seed=seed(2))
         sv.update(z_t=z_t, mean_t=mean_t, rstd_t=rstd_t, f_hi=f_hi, z_i=z_i, mean_i=mean_i, rstd_i=rstd_i,
                   z_l=z_l, mean_l=mean_l, rstd_l=rstd_l, z_v=a32, mean_v=mean_v, rstd_v=rstd_v)
-        return self.stack.forward(ar, pw["layers"], p_hid, p_att, seed0), sv
+        if taps is not None and taps.get("hidden"):
+            taps["embed"] = x32.view(B, S, H).clone()  # (the stream's fp32 buffers ping-pong between layers)
+        return self.stack.forward(ar, pw["layers"], p_hid, p_att, seed0, taps=taps), sv
 
     # ---- backward ------------------------------------------------------------------------------------------------
     def backward(self, sv, dx):

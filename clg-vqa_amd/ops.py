@@ -249,6 +249,13 @@ def attn2_fwd(qkv_hi, qkv_lo, addmask, ctx_hi, ctx_lo, lse, B, S, nh, dh, p_drop
                                        S if nq is None else nq, float(p_drop), int(seed), _stream()), "vl_attn2_fwd")
 
 
+def attn2_fwd_probs(qkv_hi, qkv_lo, addmask, ctx_hi, ctx_lo, lse, probs, B, S, nh, dh, p_drop, seed, nq=None):
+    """attn2_fwd that also writes the post-dropout probabilities to probs [B, nh, S, S] fp32 (None: plain attn2_fwd)."""
+    _lib.check(_lib.lib().vl_attn2_fwd_probs(_p(qkv_hi), _p(qkv_lo), _p(addmask), _p(ctx_hi), _p(ctx_lo), _p(lse), _p(probs),
+                                             B, S, nh, dh, S if nq is None else nq, float(p_drop), int(seed), _stream()),
+               "vl_attn2_fwd_probs")
+
+
 def attn2_bwd(qkv_hi, addmask, dctx16, lse, dqkv16, B, S, nh, dh, p_drop, seed, nq=None):
     _lib.check(_lib.lib().vl_attn2_bwd(_p(qkv_hi), _p(addmask), _p(dctx16), _p(lse), _p(dqkv16), B, S, nh, dh,
                                        S if nq is None else nq, float(p_drop), int(seed), _stream()), "vl_attn2_bwd")

@@ -165,6 +165,15 @@ int vl_attn2_fwd(const void* qkv_hi, const void* qkv_lo, const float* addmask, v
                  int64_t B, int64_t S, int64_t nh, int64_t dh, int64_t nq, float p_drop, uint64_t seed, void* stream);
 int vl_attn2_bwd(const void* qkv_hi, const float* addmask, const void* dctx16, const float* lse, void* dqkv16,
                  int64_t B, int64_t S, int64_t nh, int64_t dh, int64_t nq, float p_drop, uint64_t seed, void* stream);
+/* vl_attn2_fwd that also emits the attention probabilities the reference returns when config.visualization is set
+ * (encoders.py:286-311, 343-359): probs [B, nh, S, S] fp32, index ((b*nh + h)*S + q)*S + key, the value that multiplies V --
+ * softmax of the masked, scaled scores times the dropout keep scale (the reference returns the post-dropout tensors).
+ * Rows q in [0, nq) of every (sample, head) are written, nothing else (padded key / query slots of the kernel's tiles are
+ * not stored).  A compile-time variant of the same kernel: ctx and lse are bit-identical to vl_attn2_fwd with the same
+ * arguments.  probs must be 16-byte aligned; probs == NULL is exactly vl_attn2_fwd. */
+int vl_attn2_fwd_probs(const void* qkv_hi, const void* qkv_lo, const float* addmask, void* ctx_hi, void* ctx_lo, float* lse,
+                       float* probs, int64_t B, int64_t S, int64_t nh, int64_t dh, int64_t nq, float p_drop, uint64_t seed,
+                       void* stream);
 
 /* The op north_star names -- QKV projection + masked softmax(QK^T)V over the [text ; box] sequence (encoders.py:229-341) --
  * as one entry point per direction (SURVEY 8b vl_qkv_attention_{fwd,bwd}).  Forward = the 3-pass projection GEMM with the
@@ -175,6 +184,12 @@ int vl_attn2_bwd(const void* qkv_hi, const float* addmask, const void* dctx16, c
 int vl_qkv_attention_fwd(const void* x_hi, const void* x_lo, const void* wqkv_hi, const void* wqkv_lo, const float* bqkv,
                          const float* addmask, void* qkv_hi, void* qkv_lo, void* ctx_hi, void* ctx_lo, float* lse,
                          int64_t B, int64_t S, int64_t nh, int64_t dh, int64_t nq, float p_drop, uint64_t seed, void* stream);
+/* vl_qkv_attention_fwd through vl_attn2_fwd_probs (encoders.py:286-311, 343-359); probs == NULL: exactly
+ * vl_qkv_attention_fwd. */
+int vl_qkv_attention_fwd_probs(const void* x_hi, const void* x_lo, const void* wqkv_hi, const void* wqkv_lo, const float* bqkv,
+                               const float* addmask, void* qkv_hi, void* qkv_lo, void* ctx_hi, void* ctx_lo, float* lse,
+                               float* probs, int64_t B, int64_t S, int64_t nh, int64_t dh, int64_t nq, float p_drop,
+                               uint64_t seed, void* stream);
 int vl_qkv_attention_bwd(const void* qkv_hi, const float* addmask, const void* dctx16, const float* lse, const void* wqkv_t,
                          const float* resid32, void* dqkv16, float* dx32, int64_t B, int64_t S, int64_t nh, int64_t dh,
                          int64_t nq, float p_drop, uint64_t seed, void* stream);
@@ -379,6 +394,12 @@ enum {
   VL_LY_EV_READY = 83, /* a hipEvent_t of the caller or 0: vl_stack_fwd makes its stream wait for it before the layer's first
                           kernel (the layer's parameters / prepared weights are being written on another stream: the optimizer
                           update of the previous step running under this forward) */
+  /* Optional per-layer taps of vl_stack_fwd (0 = off; caller-owned fp32 buffers; vl_stack_bwd ignores them): what
+     BertEncoder.forward returns with output_all_encoded_layers / output_all_attention_masks (encoders.py:848-892).  Not
+     allowed on a layer that runs in the pooled-row mode. */
+  VL_LY_TAP_PROBS = 84, /* [B, nh, S, S]: the layer's attention goes through vl_qkv_attention_fwd_probs */
+  VL_LY_TAP_X1 = 85,    /* [B*S, H]: output of LayerNorm 1 = the attention sub-layer's output */
+  VL_LY_TAP_OUT = 86,   /* [B*S, H]: output of LayerNorm 2 = the feed-forward sub-layer's output */
   VL_LY_FIELDS = 96
 };
 /* Pooled-row mode (VL_ST_POOLED_ONLY): the head reads hidden_states[:, 0] only (BertTextPooler, encoders.py:597-608; M3P

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Attention core (vl_attn2_fwd / vl_attn2_bwd) on the GPU box, HIP-event timed with cold caches, against its HBM floor."""
+"""Attention core (vl_attn2_fwd / vl_attn2_bwd) on the GPU box, HIP-event timed with cold caches, against its HBM floor.
+--probs: also the emitting variant (vl_attn2_fwd_probs), whose floor includes the 4 * B * nh * S^2 bytes of P it stores."""
 import os
 import sys
 
@@ -24,6 +25,7 @@ def timeit(fn, n=30):
 
 
 def main():
+    probs = "--probs" in sys.argv[1:]
     for B, S in ((256, 56), (256, 76), (256, 120), (128, 120), (256, 140), (128, 156)):
         nh, H = 12, 768
         M = B * S
@@ -50,6 +52,12 @@ def main():
             tb = timeit(cold(lambda: ops.attn2_bwd(hi, am, d16, lse, dq, B, S, nh, 64, p, 1))) - t_z
             print("B=%d S=%d p=%.1f: fwd %.1f us (%.2f TB/s of %.0f MB)  bwd %.1f us (%.2f TB/s of %.0f MB)" % (
                 B, S, p, tf, fwd_mb / tf, fwd_mb, tb, bwd_mb / tb, bwd_mb), flush=True)
+            if probs:
+                pb = torch.empty(B, nh, S, S, device="cuda")
+                tp = timeit(cold(lambda: ops.attn2_fwd_probs(hi, lo, am, ch, cl, lse, pb, B, S, nh, 64, p, 1))) - t_z
+                pmb = fwd_mb + pb.numel() * 4 / 1e6
+                print("    emitting P: fwd %.1f us (%.2f TB/s of %.0f MB)  = plain %+.1f us" % (tp, pmb / tp, pmb, tp - tf), flush=True)
+                del pb
 
 
 if __name__ == "__main__":
