@@ -33,18 +33,10 @@
 // non-transposed layout the same way, in a second phase that owns key tiles (no cross-wave reduction, no atomics).
 //
 // Dropout on the probabilities: counter-based, one 32-bit hash per (query, key pair), regenerated in backward.
-#include "common.h"
+#include "tile.h"
 #include "../../include/vlhip.h"
 
 namespace {
-
-// timing experiments with WRONG RESULTS (variant builds only, tools/attn_exp.sh): -DVL_EXP_ATTN=<bits> takes out of the forward
-// kernel 1 = the input loads, 2 = everything between staging and the output stores, 4 = the output stores
-#ifdef VL_EXP_ATTN
-#define VL_EXP_OFF(bit) (((VL_EXP_ATTN) & (bit)) && p.S != -1)
-#else
-#define VL_EXP_OFF(bit) false
-#endif
 
 // head dim DH (64: the model configs; 32: the tiny "c1" plumbing config) is a template parameter: KS = DH / 32 k-steps
 // per Q.K^T product, DT = DH / 16 output column tiles, LDS row pitch DH * 2 + 16 bytes
@@ -59,9 +51,6 @@ template <int DH> struct Geo {
     return row * PITCH + (((2 * dt + (pp >> 1)) ^ sw(row)) << 4) + 8 * (pp & 1);
   }
 };
-
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
 
 struct Attn2Args {
   const bf16_raw* qkv_hi; const bf16_raw* qkv_lo; const float* addmask;
@@ -79,17 +68,6 @@ __device__ __forceinline__ f32x4 mfma(bf16x8 a, bf16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 __device__ __forceinline__ bf16x8 lds_frag(const unsigned char* p) { return *reinterpret_cast<const bf16x8*>(p); }
-// 8 k-values (rows r0.., r1.. of the LDS image; 4 each) of column (lane & 15) of a 16-column block: see gemm.hip tr_frag
-__device__ __forceinline__ bf16x8 tr_frag2(const unsigned char* p0, const unsigned char* p1) {
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p0);
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p1);
-  const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, v);
-}
-__device__ __forceinline__ bf16x8 zero_frag() {
-  const s16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-  return __builtin_bit_cast(bf16x8, z);
-}
 __device__ __forceinline__ bf16x8 pack8(const float* x) {
   s16x8 v;
 #pragma unroll
@@ -242,15 +220,8 @@ __global__ __launch_bounds__(NW * 64, VL_ATTN_FWD_MINW(NT, NW)) void attn2_fwd_k
   unsigned char* const dsts[4] = {sKh, sKl, sVh, sVl};
   const long lds4[4] = {ld, ld, ld, ld};
   const int rows4[4] = {S, S, S, S};
-#ifdef VL_EXP_ATTN
-  for (int m = 0; m < 4; ++m)
-    for (int i = 0; i < st.IT; ++i) st.v[m][i] = make_uint4(0u, 0u, 0u, 0u);
-#endif
-  if (!VL_EXP_OFF(1)) st.load(srcs, lds4, rows4, tid);
+  st.load(srcs, lds4, rows4, tid);
   bf16x8 qh[KS], ql[KS];
-#ifdef VL_EXP_ATTN
-  for (int ks = 0; ks < KS; ++ks) qh[ks] = ql[ks] = zero_frag();
-#endif
   auto load_q = [&](int qt) {
     const int q = qt * 16 + l15, qr = q < S ? q : 0;  // (rows past S: any finite values, their results are never stored)
 #pragma unroll
@@ -262,7 +233,7 @@ __global__ __launch_bounds__(NW * 64, VL_ATTN_FWD_MINW(NT, NW)) void attn2_fwd_k
   // query tiles go to waves round-robin from a per-workgroup start: when NT is not a multiple of NW (9 tiles on 8 waves) the
   // wave with one tile more is a different one -- on a different SIMD -- in the workgroups that share a CU
   const int w0 = NT % NW == 0 ? wave : (wave + (int)((blockIdx.x * 0x9E3779B1u) >> 16)) & (NW - 1);
-  if (w0 < nqt && !VL_EXP_OFF(1)) load_q(w0);
+  if (w0 < nqt) load_q(w0);
   if (tid < Spad) smask[tid] = tid < S ? mask_v : -INFINITY;
   st.store(dsts, rows4, tid);
   __syncthreads();
@@ -272,7 +243,6 @@ __global__ __launch_bounds__(NW * 64, VL_ATTN_FWD_MINW(NT, NW)) void attn2_fwd_k
     f32x4 o[DT];
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (!VL_EXP_OFF(2)) {
     f32x4 sc[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
@@ -289,7 +259,7 @@ __global__ __launch_bounds__(NW * 64, VL_ATTN_FWD_MINW(NT, NW)) void attn2_fwd_k
     }
     // the wave's next query tile arrives under the softmax and P.V of this one (9 key tiles: no registers to spare under the
     // 128-VGPR budget of two 8-wave workgroups per CU; loaded at the end of the trip instead)
-    if (NT != 9 && qt + NW < nqt && !VL_EXP_OFF(1)) load_q(qt + NW);
+    if (NT != 9 && qt + NW < nqt) load_q(qt + NW);
     // softmax over the keys of query q: this lane holds keys 16 t + 4 g + r
     float m = -INFINITY;
 #pragma unroll
@@ -368,17 +338,16 @@ __global__ __launch_bounds__(NW * 64, VL_ATTN_FWD_MINW(NT, NW)) void attn2_fwd_k
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
         const int r0 = Geo<DH>::tr_off(vr0, dt, pp), r1 = Geo<DH>::tr_off(vr1, dt, pp);
-        const bf16x8 vh = tr_frag2(sVh + r0, sVh + r1);
-        const bf16x8 vl = tr_frag2(sVl + r0, sVl + r1);
+        const bf16x8 vh = tr_frag(sVh + r0, sVh + r1);
+        const bf16x8 vl = tr_frag(sVl + r0, sVl + r1);
         o[dt] = mfma(vh, pl, o[dt]);
         o[dt] = mfma(vl, ph, o[dt]);
         o[dt] = mfma(vh, ph, o[dt]);
       }
       asm volatile("" ::: "memory");
     }
-    }  // (VL_EXP_OFF(2))
     {
-      const bool ok = q < p.nq && !VL_EXP_OFF(4);
+      const bool ok = q < p.nq;
       const long off = ((long)b * p.ctx_rows + (ok ? q : 0)) * p.H + h * DH;
 #pragma unroll
       for (int m = 0; m < DT / 2; ++m) {
@@ -392,7 +361,7 @@ __global__ __launch_bounds__(NW * 64, VL_ATTN_FWD_MINW(NT, NW)) void attn2_fwd_k
         }
       }
     }
-    if (NT == 9 && qt + NW < nqt && !VL_EXP_OFF(1)) load_q(qt + NW);
+    if (NT == 9 && qt + NW < nqt) load_q(qt + NW);
   }
 }
 
@@ -514,7 +483,7 @@ __global__ __launch_bounds__(NW * 64, VL_ATTN_BWD_MINW(NT, NW)) void attn2_bwd_k
       const int kr0 = 16 * t0 + 4 * g + qq, kr1 = 16 * t1 + 4 * g + qq;
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt)
-        o[dt] = mfma(tr_frag2(sK + Geo<DH>::tr_off(kr0, dt, pp), sK + Geo<DH>::tr_off(kr1, dt, pp)), dsb, o[dt]);
+        o[dt] = mfma(tr_frag(sK + Geo<DH>::tr_off(kr0, dt, pp), sK + Geo<DH>::tr_off(kr1, dt, pp)), dsb, o[dt]);
       asm volatile("" ::: "memory");
     }
     store_row_bf16<DT>(dq_base + (long)(q < S ? q : 0) * ld, o, g, q < S);
@@ -568,8 +537,8 @@ __global__ __launch_bounds__(NW * 64, VL_ATTN_BWD_MINW(NT, NW)) void attn2_bwd_k
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
         const int r0 = Geo<DH>::tr_off(qr0, dt, pp), r1 = Geo<DH>::tr_off(qr1, dt, pp);
-        dV[dt] = mfma(tr_frag2(sO + r0, sO + r1), bpd, dV[dt]);
-        dK[dt] = mfma(tr_frag2(sQ + r0, sQ + r1), bds, dK[dt]);
+        dV[dt] = mfma(tr_frag(sO + r0, sO + r1), bpd, dV[dt]);
+        dK[dt] = mfma(tr_frag(sQ + r0, sQ + r1), bds, dK[dt]);
       }
     }
     {

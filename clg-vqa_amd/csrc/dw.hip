@@ -18,15 +18,10 @@
 // the chip, the rest stays with the backward critical path on the main stream.
 #include <type_traits>
 
-#include "common.h"
+#include "tile.h"
 #include "../../include/vlhip.h"
 
 namespace {
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* glb_ptr_t;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
 
 constexpr int MAXT = 8;
 
@@ -91,10 +86,7 @@ __global__ __launch_bounds__(256) void transpose_blocked_kernel(TrArgs a) {
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
       const unsigned char* p0 = tile + (32 * half + 8 * g + qq) * TP + (16 * wave + 4 * pp) * 2;
-      const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p0);
-      const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p0 + 4 * TP));
-      const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-      *reinterpret_cast<s16x8*>(dst + 32 * half + 8 * g) = v;
+      *reinterpret_cast<bf16x8*>(dst + 32 * half + 8 * g) = tr_frag(p0, p0 + 4 * TP);
     }
     __syncthreads();  // the tile is rewritten by the next unit
   }
@@ -172,10 +164,6 @@ struct DwArgs { DwProb p[MAXT]; int nprob; int nk; int total_tiles; int accumula
 constexpr int SK_SLOT_F4 = 34 * 512;              // float4 per slot: 32 accumulator registers + 2 bias-sum registers per thread
 constexpr long SK_SLOT_FLOATS = 4L * SK_SLOT_F4;  // 278 528 bytes
 
-__device__ __forceinline__ int swz3(int row) {
-  return ((row >> 1) & 1) | (((row >> 3) & 1) << 1) | ((((row >> 4) ^ (row >> 2)) & 1) << 2);
-}
-
 // TN = true: the operands are the ROW-MAJOR activations themselves (dY [rows, N_out], X [rows, K_in], rows = the reduction
 // dimension) -- no K-major images, no re-layout pass.  A K-tile is 64 rows; a half-tile is [64 rows][128 columns] (256-B
 // rows, 16 KB like the NT half-tile, so staging units, DMA instruction counts and the vmcnt accounting are unchanged);
@@ -193,7 +181,7 @@ __device__ __forceinline__ int swz3(int row) {
 // the results are complete after the s_waitcnt lgkmcnt(0) that opens every MFMA section.
 typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 template <int OFF>
-__device__ __forceinline__ bf16x8 tr_frag(unsigned lds_addr) {
+__device__ __forceinline__ bf16x8 tr_frag_asm(unsigned lds_addr) {
   static_assert(OFF >= 0 && OFF + 4 * 256 < 65536, "LDS offset field");
   typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
   u32x2 lo, hi;
@@ -204,7 +192,7 @@ __device__ __forceinline__ bf16x8 tr_frag(unsigned lds_addr) {
 }
 template <bool T, int OFF>
 __device__ __forceinline__ bf16x8 dw_frag(unsigned lds_addr) {  // lds_addr: this lane's fragment address in the current stage
-  if constexpr (T) return tr_frag<OFF>(lds_addr);
+  if constexpr (T) return tr_frag_asm<OFF>(lds_addr);
   else return *(const __attribute__((address_space(3))) bf16x8*)(uintptr_t)(lds_addr + OFF);
 }
 // s + one * the 8 bf16 values (fp32 accumulation); one = bf16 {1, 1} on the K-tiles this tile sums, {0, 0} on the others
@@ -246,9 +234,7 @@ __global__ __launch_bounds__(512) void dw_grouped_kernel(DwArgs ga) {
   // XCD-contiguous virtual workgroup index: neighbours in the work list (tiles that share an operand panel; stream-K:
   // the two sides of a hand-off) sit on one XCD, i.e. behind one L2
   const int nwg = SK ? (int)gridDim.x : ga.total_tiles;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int swz = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int swz = xcd_tile(blockIdx.x, nwg);
   const int nk_tile = ga.nk;
   // this workgroup's range of the iteration space
   long it, it_end;
@@ -605,9 +591,6 @@ extern "C" int64_t vl_dw_streamk_ws_bytes(int64_t budget) {
 
 // tab: HOST array of n x VL_TR_FIELDS int64 {src, ld, N, dst, colsum_partial (0 = none), 0}
 extern "C" int vl_transpose_blocked(const int64_t* tab, int64_t n, int64_t M, int64_t max_blocks, void* stream) {
-#ifdef VL_EXPERIMENT_SKIP_RELAYOUT  // timing experiment only (wrong results): what the step costs without the re-layout
-  if (M > 4096) return 0;
-#endif
   VL_CHECK_ARG(tab && n >= 1 && n <= MAXT && M >= 1 && M < (1LL << 31), "vl_transpose_blocked: bad arguments");
   TrArgs a{};
   a.n = (int)n; a.M = (int)M; a.mblocks = (int)((M + 63) / 64);
@@ -670,17 +653,7 @@ extern "C" int vl_colreduce_multi(const int64_t* tab, int64_t n, int accumulate,
 // (rowmajor: {dY, lda, X, ldb, out, ldo, mask, M, N, colsum partials [ceil(N / 256), M] or 0})
 template <int MODE, bool SK>
 static int dw_launch_t(const DwArgs& a, int grid, const char* fn, void* stream) {
-  const size_t lds = 2 * 65536;
-  static bool attr_set = false;  // per instantiation; idempotent, so a race only repeats the call
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dw_grouped_kernel<MODE, SK>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return vl_set_error(-3, "%s: hipFuncSetAttribute: %s", fn, hipGetErrorString(e));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((dw_grouped_kernel<MODE, SK>), dim3(grid), dim3(512), lds, (hipStream_t)stream, a);
-  VL_CHECK_LAUNCH(fn);
-  return 0;
+  return launch_dyn_lds<&dw_grouped_kernel<MODE, SK>>(fn, dim3(grid), dim3(512), 2 * 65536, (hipStream_t)stream, a);
 }
 
 // budget > 0: the stream-K form on `budget` workgroups with the caller's workspace `ws` (vl_dw_streamk_ws_bytes(budget)

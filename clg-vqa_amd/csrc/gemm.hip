@@ -29,18 +29,9 @@
 
 // Only the explicit fmaf()s fuse: which a * b + c the optimizer contracts differs between the unrolled instances of an
 // epilogue and between tile configurations, and the epilogues of all configurations are tested bit-identical.
-#ifndef VL_GEMM_CONTRACT_FAST  // (A/B builds only)
 #pragma clang fp contract(off)
-#endif
-#include "common.h"
+#include "tile.h"
 #include "../../include/vlhip.h"
-
-// (timing experiment, WRONG RESULTS: -DVL_EXP_NO_STORE keeps the epilogue's arithmetic and loads but never executes its stores)
-#ifdef VL_EXP_NO_STORE
-#define VL_EXP_ST if (p.K == -1)
-#else
-#define VL_EXP_ST
-#endif
 
 namespace {
 
@@ -118,7 +109,7 @@ __device__ __forceinline__ void epilogue_store4(const GemmArgs& p, float* out32,
         const float4 r = has_rq ? rq : *reinterpret_cast<const float4*>(p.resid + o);
         v[0] += r.x; v[1] += r.y; v[2] += r.z; v[3] += r.w;
       }
-      VL_EXP_ST *reinterpret_cast<float4*>(out32 + o) = make_float4(v[0], v[1], v[2], v[3]);
+      *reinterpret_cast<float4*>(out32 + o) = make_float4(v[0], v[1], v[2], v[3]);
     } else {
       const long o = (long)m * p.ld16 + n0;
       ushort4 hi, lo;
@@ -128,26 +119,26 @@ __device__ __forceinline__ void epilogue_store4(const GemmArgs& p, float* out32,
 #pragma unroll
         for (int t = 0; t < 4; ++t) gelu_erf_both(v[t], y[t], d[t]);
         u.x = f32_to_bf16(d[0]); u.y = f32_to_bf16(d[1]); u.z = f32_to_bf16(d[2]); u.w = f32_to_bf16(d[3]);
-        VL_EXP_ST *reinterpret_cast<ushort4*>(p.aux16 + o) = u;
+        *reinterpret_cast<ushort4*>(p.aux16 + o) = u;
         split_bf16(y[0], hi.x, lo.x); split_bf16(y[1], hi.y, lo.y);
         split_bf16(y[2], hi.z, lo.z); split_bf16(y[3], hi.w, lo.w);
-        VL_EXP_ST *reinterpret_cast<ushort4*>(p.out_hi + o) = hi;
-        VL_EXP_ST *reinterpret_cast<ushort4*>(p.out_lo + o) = lo;
+        *reinterpret_cast<ushort4*>(p.out_hi + o) = hi;
+        *reinterpret_cast<ushort4*>(p.out_lo + o) = lo;
       } else if (EPI == VL_EPI_DGELU_BF16) {
         const ushort4 u = *reinterpret_cast<const ushort4*>(p.aux16 + o);
         hi.x = f32_to_bf16(v[0] * bf16_to_f32(u.x));
         hi.y = f32_to_bf16(v[1] * bf16_to_f32(u.y));
         hi.z = f32_to_bf16(v[2] * bf16_to_f32(u.z));
         hi.w = f32_to_bf16(v[3] * bf16_to_f32(u.w));
-        VL_EXP_ST *reinterpret_cast<ushort4*>(p.out_hi + o) = hi;
+        *reinterpret_cast<ushort4*>(p.out_hi + o) = hi;
       } else if (EPI == VL_EPI_BF16) {
         hi.x = f32_to_bf16(v[0]); hi.y = f32_to_bf16(v[1]); hi.z = f32_to_bf16(v[2]); hi.w = f32_to_bf16(v[3]);
-        VL_EXP_ST *reinterpret_cast<ushort4*>(p.out_hi + o) = hi;
+        *reinterpret_cast<ushort4*>(p.out_hi + o) = hi;
       } else {  // VL_EPI_SPLIT
         split_bf16(v[0], hi.x, lo.x); split_bf16(v[1], hi.y, lo.y);
         split_bf16(v[2], hi.z, lo.z); split_bf16(v[3], hi.w, lo.w);
-        VL_EXP_ST *reinterpret_cast<ushort4*>(p.out_hi + o) = hi;
-        VL_EXP_ST *reinterpret_cast<ushort4*>(p.out_lo + o) = lo;
+        *reinterpret_cast<ushort4*>(p.out_hi + o) = hi;
+        *reinterpret_cast<ushort4*>(p.out_lo + o) = lo;
       }
       if (p.img || want_cs) {
         const bf16_raw h4[4] = {hi.x, hi.y, hi.z, hi.w};
@@ -239,13 +230,13 @@ __device__ __forceinline__ void epilogue_store8(const GemmArgs& p, float* out32,
     for (int t = 0; t < 8; ++t) gelu_erf_both(x[t], y[t], d[t]);
     u0.x = f32_to_bf16(d[0]); u0.y = f32_to_bf16(d[1]); u0.z = f32_to_bf16(d[2]); u0.w = f32_to_bf16(d[3]);
     u1.x = f32_to_bf16(d[4]); u1.y = f32_to_bf16(d[5]); u1.z = f32_to_bf16(d[6]); u1.w = f32_to_bf16(d[7]);
-    VL_EXP_ST *reinterpret_cast<uint4*>(p.aux16 + o) = pack8(u0, u1);
+    *reinterpret_cast<uint4*>(p.aux16 + o) = pack8(u0, u1);
     split_bf16(y[0], h0.x, l0.x); split_bf16(y[1], h0.y, l0.y);
     split_bf16(y[2], h0.z, l0.z); split_bf16(y[3], h0.w, l0.w);
     split_bf16(y[4], h1.x, l1.x); split_bf16(y[5], h1.y, l1.y);
     split_bf16(y[6], h1.z, l1.z); split_bf16(y[7], h1.w, l1.w);
-    VL_EXP_ST *reinterpret_cast<uint4*>(p.out_hi + o) = pack8(h0, h1);
-    VL_EXP_ST *reinterpret_cast<uint4*>(p.out_lo + o) = pack8(l0, l1);
+    *reinterpret_cast<uint4*>(p.out_hi + o) = pack8(h0, h1);
+    *reinterpret_cast<uint4*>(p.out_lo + o) = pack8(l0, l1);
   } else if (EPI == VL_EPI_DGELU_BF16) {
     const uint4 uu = has_uq ? uq : *reinterpret_cast<const uint4*>(p.aux16 + o);  // (preloaded: see epilogue_store4's residual)
     const unsigned w[4] = {uu.x, uu.y, uu.z, uu.w};
@@ -256,16 +247,16 @@ __device__ __forceinline__ void epilogue_store8(const GemmArgs& p, float* out32,
       r[2 * t + 1] = f32_to_bf16(x[2 * t + 1] * __uint_as_float(w[t] & 0xFFFF0000u));
     }
     h0.x = r[0]; h0.y = r[1]; h0.z = r[2]; h0.w = r[3]; h1.x = r[4]; h1.y = r[5]; h1.z = r[6]; h1.w = r[7];
-    VL_EXP_ST *reinterpret_cast<uint4*>(p.out_hi + o) = pack8(h0, h1);
+    *reinterpret_cast<uint4*>(p.out_hi + o) = pack8(h0, h1);
   } else if (EPI == VL_EPI_BF16) {
     h0.x = f32_to_bf16(x[0]); h0.y = f32_to_bf16(x[1]); h0.z = f32_to_bf16(x[2]); h0.w = f32_to_bf16(x[3]);
     h1.x = f32_to_bf16(x[4]); h1.y = f32_to_bf16(x[5]); h1.z = f32_to_bf16(x[6]); h1.w = f32_to_bf16(x[7]);
-    VL_EXP_ST *reinterpret_cast<uint4*>(p.out_hi + o) = pack8(h0, h1);
+    *reinterpret_cast<uint4*>(p.out_hi + o) = pack8(h0, h1);
   } else {  // VL_EPI_SPLIT
     split_bf16(x[0], h0.x, l0.x); split_bf16(x[1], h0.y, l0.y); split_bf16(x[2], h0.z, l0.z); split_bf16(x[3], h0.w, l0.w);
     split_bf16(x[4], h1.x, l1.x); split_bf16(x[5], h1.y, l1.y); split_bf16(x[6], h1.z, l1.z); split_bf16(x[7], h1.w, l1.w);
-    VL_EXP_ST *reinterpret_cast<uint4*>(p.out_hi + o) = pack8(h0, h1);
-    VL_EXP_ST *reinterpret_cast<uint4*>(p.out_lo + o) = pack8(l0, l1);
+    *reinterpret_cast<uint4*>(p.out_hi + o) = pack8(h0, h1);
+    *reinterpret_cast<uint4*>(p.out_lo + o) = pack8(l0, l1);
   }
   if (p.img || want_cs) {
     const bf16_raw h8[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
@@ -290,9 +281,6 @@ __device__ __forceinline__ void epilogue_store8(const GemmArgs& p, float* out32,
 // ---------------------------------------------------------------------------------------------------------------
 // fast path: 256 x BN tile, LDS-DMA staging, double-buffered
 // ---------------------------------------------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* glb_ptr_t;
-
 template <int NSPLIT, int EPI, int BN, int WM>
 __global__ __launch_bounds__(WM * 256, WM) void gemm2_kernel(GemmArgs p) {
   constexpr int BM2 = 256, NT = BN / 64;                  // 16-wide n-tiles per wave (wave tile 256/WM x BN/4)
@@ -314,10 +302,7 @@ __global__ __launch_bounds__(WM * 256, WM) void gemm2_kernel(GemmArgs p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
 
-  const int nwg = p.tiles_m * p.tiles_n;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-  const int swz = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+  const int swz = xcd_tile(blockIdx.x, p.tiles_m * p.tiles_n);
   const int tm = swz / p.tiles_n, tn = swz - tm * p.tiles_n;
   const int row0 = tm * BM2, col0 = tn * BN;
   const int kbeg = blockIdx.y * p.k_len;
@@ -460,49 +445,10 @@ __global__ __launch_bounds__(WM * 256, WM) void gemm2_kernel(GemmArgs p) {
 //    B0 stays in registers for phase 3 -- re-staged in phases 2, 3; B1: phase 1 -> next phase 0; A1: phase 2 ->
 //    next phase 1).
 // Quadrant order (0,0) (0,1) (1,1) (1,0): consecutive phases share the A or the B sub-tile.
-// Bank swizzle f(row) (XOR on the 16-B chunk index, applied on the DMA source address and undone by the reads) is
-// conflict-free both for 16 consecutive rows and for the permuted rows {0-3, 8-11, 16-19, 24-27} + 4*(j&1) that the
-// paired n-tiles of the 16-bit epilogues read (see gemm2_kernel).
+// Bank swizzle: swz3 (tile.h).
+// A 5-slot LDS ring per operand (all 160 KB, every half-tile issued two phases earlier) measured no difference to this
+// 4-slot one (two K-tiles resident, 128 KB at 256 x 256) and was removed: profiles/r03_ab_log.txt section 9.
 // ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int swz3(int row) {
-  return ((row >> 1) & 1) | (((row >> 3) & 1) << 1) | ((((row >> 4) ^ (row >> 2)) & 1) << 2);
-}
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-  static_assert(N >= 0 && N <= 12, "unsupported count");
-  if (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (N == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-  if (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-  if (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-  if (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  if (N == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-  if (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  if (N == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-  if (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  if (N == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-  if (N == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-  if (N == 11) asm volatile("s_waitcnt vmcnt(11)" ::: "memory");
-  if (N == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-}
-
-// RING (VL_GEMM_RING): LDS slots per operand, each one half-tile.  4 = two K-tiles resident (128 KB at 256 x 256): a half-tile
-// is issued 4 - 5 phases (one K-tile) before its first read.  5 = all 160 KB of the CU's LDS: every half-tile is issued TWO
-// PHASES EARLIER -- 7 - 8 phases before its read -- because the timing experiments (profiles/r03_ab_log.txt section 7) put 11 - 21 %
-// of every product into waits for operand DMA: one K-tile of prefetch distance is shorter than the memory latency of the
-// loaded chip.  Slot of half h of K-tile kt: (2 kt + h) mod RING, per operand.  Schedule for RING = 5, K-tile kt:
-//      phase 0: read B0, A0 (kt) | issue A0 (kt + 2)      phase 1: read B1 (kt) | issue B0 (kt + 2)
-//      phase 2: read A1 (kt)     | issue B1 (kt + 2)      phase 3:              | issue A1 (kt + 2)
-//  * WAR: A0 (kt + 2) takes the slot of A1 (kt - 1) (last read: phase 2 of kt - 1), B0 (kt + 2) that of B1 (kt - 1) (phase 1 of
-//    kt - 1), B1 (kt + 2) that of B0 (kt) (phase 0), A1 (kt + 2) that of A0 (kt) (phase 0): always >= 2 phases after the read,
-//    the same margin as the 4-slot ring.
-//  * RAW: after its own issue every phase waits until at most the SIX youngest half-tiles are outstanding, so a half-tile
-//    issued in phase q has landed by the wait of phase q + 6 and is first read in phase q + 7 or q + 8, behind the barriers of
-//    phase q + 6 (also with the one-barrier stagger of waves 4 - 7).
-// Measured (same box, profiles/r03_ab_log.txt section 9): no difference -- QKV 140.2 / 141.2 vs 150.4 / 138.6 us, FFN2 215 / 208 vs
-// 205 / 210, step 16.07 / 16.13 vs 16.10 / 16.09 ms.  The cost the "no DMA" experiment exposes is therefore NOT prefetch distance
-// (the data is there in time); the 4-slot ring stays the default (128 KB), the 5-slot path stays tested behind the macro.
-#ifndef VL_GEMM_RING
-#define VL_GEMM_RING 4
-#endif
 
 // PERSIST: the grid is a fixed number of workgroups G (<= the CU count); workgroup w runs tiles w, w + G, w + 2G, ... (the
 // XCD-contiguous tile order is kept: tile t and t + G land on the same XCD when G % 8 == 0).  Between two tiles the DMA
@@ -526,9 +472,6 @@ __global__ __launch_bounds__(512) void gemm3_kernel(GemmArgs p) {
   constexpr int KSTEP = NSPLIT == 3 ? 32 : 64;
   constexpr bool PAIR = (EPI != VL_EPI_F32);
   constexpr int NJP = PAIR ? (NJ & ~1) : 0;                 // n-tiles [0, NJP) of a quadrant are paired
-  constexpr int RING = VL_GEMM_RING;                        // LDS slots per operand (see above)
-  constexpr int SLOT_A = AH * 128, SLOT_B = BH * 128;       // RING == 5: A ring at 0, B ring behind it
-  constexpr int RING_B0 = RING * SLOT_A;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -537,6 +480,8 @@ __global__ __launch_bounds__(512) void gemm3_kernel(GemmArgs p) {
 
   const int nwg = p.tiles_m * p.tiles_n;
   const int nk = p.K / KSTEP;
+  // (xcd_tile of tile.h, written out: its q / r are computed once here, outside set_tile -- the call per tile moved
+  // instructions in all 38 instances of this kernel and changed the kernel descriptors of two persistent ones)
   const int q8 = nwg >> 3, r8 = nwg & 7;
   int row0, col0, tm;
   // DMA sources: half-tile x in {A0, A1, B0, B1}; unit u = wave + 8*j (8 rows x 128 B); lane -> (row, physical chunk)
@@ -589,25 +534,6 @@ __global__ __launch_bounds__(512) void gemm3_kernel(GemmArgs p) {
     if (issued) G3_WAIT_YOUNGER(2, 2);                                                                           \
     else wait_vmcnt<0>();                                                                                        \
   } while (0)
-  // RING == 5: half-tile x of K-tile kt into ring slot `slot` (a scalar) of its operand
-#define G5_ISSUE(x, kt, slot)                                                                                    \
-  do {                                                                                                           \
-    unsigned char* dst_ = smem + ((x) >= 2 ? RING_B0 + (slot) * SLOT_B : (slot) * SLOT_A);                       \
-    __builtin_amdgcn_global_load_lds((glb_ptr_t)(src[x][0] + (long)(kt) * KSTEP), (lds_ptr_t)(dst_ + wave * 1024), 16, 0, 0); \
-    if (!(late && ((BSHORT && (x) >= 2) || (ASHORT && (x) == 1))))                                               \
-      __builtin_amdgcn_global_load_lds((glb_ptr_t)(src[x][1] + (long)(kt) * KSTEP), (lds_ptr_t)(dst_ + (wave + 8) * 1024), 16, 0, 0); \
-  } while (0)
-  // ... wait until at most the youngest (nA0 first-half A + nA1 second-half A + nB B) half-tiles are outstanding
-#define G5_WAIT_YOUNGER(nA0, nA1, nB)                                                                            \
-  do {                                                                                                           \
-    if (late) wait_vmcnt<2 * (nA0) + (ASHORT ? 1 : 2) * (nA1) + (BSHORT ? 1 : 2) * (nB)>();                      \
-    else wait_vmcnt<2 * ((nA0) + (nA1) + (nB))>();                                                               \
-  } while (0)
-#define G5_WAIT(issued, nA0, nA1, nB)                                                                            \
-  do {                                                                                                           \
-    if (issued) G5_WAIT_YOUNGER(nA0, nA1, nB);                                                                   \
-    else wait_vmcnt<0>();                                                                                        \
-  } while (0)
 
   f32x4 acc[2][2][MI][NJ];  // [1][*][i >= MI1] unused
 
@@ -631,51 +557,24 @@ __global__ __launch_bounds__(512) void gemm3_kernel(GemmArgs p) {
   }
 
   bf16x8 fa[MI][2], fb0[NJ][2], fb1[NJ][2];
-#ifdef VL_EXP_NO_READS
-#define G3_RD_GUARD if (kt == 0)
-#else
-#define G3_RD_GUARD
-#endif
 #define G3_READ_A(st, qm)                                                                                        \
-  G3_RD_GUARD _Pragma("unroll") for (int i = 0; i < ((qm) == 0 ? MI : MI1); ++i) {                                          \
+  _Pragma("unroll") for (int i = 0; i < ((qm) == 0 ? MI : MI1); ++i) {                                          \
     fa[i][0] = *reinterpret_cast<const bf16x8*>((st) + (qm) * OFF_A1 + a_o[(qm) % QA][i][0]);                    \
     fa[i][1] = *reinterpret_cast<const bf16x8*>((st) + (qm) * OFF_A1 + a_o[(qm) % QA][i][1]);                    \
   }
 #define G3_READ_B(st, qn, fb)                                                                                    \
-  G3_RD_GUARD _Pragma("unroll") for (int j = 0; j < NJ; ++j) {                                                              \
+  _Pragma("unroll") for (int j = 0; j < NJ; ++j) {                                                              \
     fb[j][0] = *reinterpret_cast<const bf16x8*>((st) + OFF_B0 + (qn) * (BH * 128) + b_o[j][0]);                  \
     fb[j][1] = *reinterpret_cast<const bf16x8*>((st) + OFF_B0 + (qn) * (BH * 128) + b_o[j][1]);                  \
   }
-#define G5_READ_A(pa, qm)                                                                                        \
-  G3_RD_GUARD _Pragma("unroll") for (int i = 0; i < ((qm) == 0 ? MI : MI1); ++i) {                              \
-    fa[i][0] = *reinterpret_cast<const bf16x8*>((pa) + a_o[(qm) % QA][i][0]);                                    \
-    fa[i][1] = *reinterpret_cast<const bf16x8*>((pa) + a_o[(qm) % QA][i][1]);                                    \
-  }
-#define G5_READ_B(pb, fb)                                                                                        \
-  G3_RD_GUARD _Pragma("unroll") for (int j = 0; j < NJ; ++j) {                                                  \
-    fb[j][0] = *reinterpret_cast<const bf16x8*>((pb) + b_o[j][0]);                                               \
-    fb[j][1] = *reinterpret_cast<const bf16x8*>((pb) + b_o[j][1]);                                               \
-  }
   // 1 pass: [0] / [1] are the two 32-deep k halves of the row; 3 passes: [0] = hi, [1] = lo of one 32-deep k step and
   // the products are issued product-major so that dependent accumulations are MI*NJ MFMAs apart
-  // (timing experiments, WRONG RESULTS, only meaningful together with VL_EXP_NO_DMA + VL_EXP_NO_READS: -DVL_EXP_NO_BARRIER drops the
-  // two barriers around every MFMA section, -DVL_EXP_NO_PRIO the priority flips)
-#ifdef VL_EXP_NO_BARRIER
-#define G3_BAR() do { } while (0)
-#else
-#define G3_BAR() __builtin_amdgcn_s_barrier()
-#endif
-#ifdef VL_EXP_NO_PRIO
-#define G3_PRIO(x) do { } while (0)
-#else
-#define G3_PRIO(x) __builtin_amdgcn_s_setprio(x)
-#endif
 #define G3_MFMA(qm, qn, fb)                                                                                      \
   do {                                                                                                           \
-    G3_BAR();                                                                                                    \
+    __builtin_amdgcn_s_barrier();                                                                                \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                           \
     __builtin_amdgcn_sched_barrier(0);                                                                           \
-    G3_PRIO(1);                                                                                                  \
+    __builtin_amdgcn_s_setprio(1);                                                                               \
     if (NSPLIT == 1) {                                                                                           \
       _Pragma("unroll") for (int kk = 0; kk < 2; ++kk)                                                           \
       _Pragma("unroll") for (int i = 0; i < ((qm) == 0 ? MI : MI1); ++i)                                         \
@@ -692,26 +591,20 @@ __global__ __launch_bounds__(512) void gemm3_kernel(GemmArgs p) {
       _Pragma("unroll") for (int j = 0; j < NJ; ++j)                                                             \
           acc[qm][qn][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j][0], fa[i][0], acc[qm][qn][i][j], 0, 0, 0); \
     }                                                                                                            \
-    G3_PRIO(0);                                                                                                  \
+    __builtin_amdgcn_s_setprio(0);                                                                               \
     __builtin_amdgcn_sched_barrier(0);                                                                           \
-    G3_BAR();                                                                                                    \
+    __builtin_amdgcn_s_barrier();                                                                                \
   } while (0)
 
   // prologue: K-tile 0 complete, A0 / B0 of K-tile 1 in flight
-  // (RING == 5: K-tile 0 complete, ALL of K-tile 1 in flight, issued in the loop's order A0, B0, B1, A1)
 #define G3_PROLOGUE_ISSUE()                                                                                      \
   do {                                                                                                           \
-    if (RING == 5) {                                                                                             \
-      G5_ISSUE(0, 0, 0); G5_ISSUE(2, 0, 0); G5_ISSUE(3, 0, 1); G5_ISSUE(1, 0, 1);                                \
-      if (nk > 1) { G5_ISSUE(0, 1, 2); G5_ISSUE(2, 1, 2); G5_ISSUE(3, 1, 3); G5_ISSUE(1, 1, 3); }                \
-    } else {                                                                                                     \
-      G3_ISSUE(0, 0); G3_ISSUE(2, 0); G3_ISSUE(3, 0); G3_ISSUE(1, 0);                                            \
-      if (nk > 1) { G3_ISSUE(0, 1); G3_ISSUE(2, 1); }                                                            \
-    }                                                                                                            \
+    G3_ISSUE(0, 0); G3_ISSUE(2, 0); G3_ISSUE(3, 0); G3_ISSUE(1, 0);                                              \
+    if (nk > 1) { G3_ISSUE(0, 1); G3_ISSUE(2, 1); }                                                              \
   } while (0)
 #define G3_PROLOGUE_WAIT()                                                                                       \
   do {                                                                                                           \
-    if (nk > 1) { if (RING == 5) G5_WAIT_YOUNGER(1, 1, 2); else G3_WAIT_YOUNGER(1, 1); }                          \
+    if (nk > 1) G3_WAIT_YOUNGER(1, 1);                                                                           \
     else wait_vmcnt<0>();                                                                                        \
     __builtin_amdgcn_s_barrier();                                                                                \
     if (late) __builtin_amdgcn_s_barrier(); /* stagger */                                                        \
@@ -730,53 +623,9 @@ __global__ __launch_bounds__(512) void gemm3_kernel(GemmArgs p) {
       for (int i = 0; i < MI; ++i)
 #pragma unroll
         for (int j = 0; j < NJ; ++j) acc[a_][b_][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  // (timing experiments, WRONG RESULTS: -DVL_EXP_NO_DMA: no operand DMA inside the K loop; -DVL_EXP_NO_READS: no LDS fragment
-  // reads inside it; what is left of the loop is MFMA sections + barriers)
-#if defined(VL_EXP_NO_DMA) || defined(VL_EXP_NO_READS)
-#pragma message("gemm3_kernel: timing-experiment build -- results are wrong")
-#endif
-  if constexpr (RING == 5) {
-    int ia = 0, ib = 0;  // ring slots of A0 (kt) / B0 (kt): (2 kt) mod 5
-    for (int kt = 0; kt < nk; ++kt) {
-#ifdef VL_EXP_NO_DMA
-      const bool n2 = false;
-#else
-      const bool n2 = kt + 2 < nk;
-#endif
-      const int ia1 = ia + 1 >= 5 ? ia - 4 : ia + 1, ia4 = ia + 4 >= 5 ? ia - 1 : ia + 4;  // slots of A1 (kt), A0 (kt + 2)
-      const int ib1 = ib + 1 >= 5 ? ib - 4 : ib + 1, ib4 = ib + 4 >= 5 ? ib - 1 : ib + 4;  //          B1 (kt), B0 (kt + 2)
-      // phase 0: quadrant (0,0)
-      G5_READ_B(smem + RING_B0 + ib * SLOT_B, fb0);
-      __builtin_amdgcn_sched_barrier(0);
-      G5_READ_A(smem + ia * SLOT_A, 0);
-      if (n2) G5_ISSUE(0, kt + 2, ia4);
-      G5_WAIT(n2, 2, 2, 2);
-      G3_MFMA(0, 0, fb0);
-      // phase 1: quadrant (0,1)
-      G5_READ_B(smem + RING_B0 + ib1 * SLOT_B, fb1);
-      if (n2) G5_ISSUE(2, kt + 2, ib4);
-      G5_WAIT(n2, 2, 1, 3);
-      G3_MFMA(0, 1, fb1);
-      // phase 2: quadrant (1,1)
-      G5_READ_A(smem + ia1 * SLOT_A, 1);
-      if (n2) G5_ISSUE(3, kt + 2, ib);  // (B1 (kt + 2): the slot B0 (kt) was read from in phase 0)
-      G5_WAIT(n2, 1, 1, 4);
-      G3_MFMA(1, 1, fb1);
-      // phase 3: quadrant (1,0)
-      if (n2) G5_ISSUE(1, kt + 2, ia);  // (A1 (kt + 2): the slot of A0 (kt))
-      G5_WAIT(n2, 1, 2, 3);
-      G3_MFMA(1, 0, fb0);
-      ia = ia + 2 >= 5 ? ia - 3 : ia + 2;
-      ib = ib + 2 >= 5 ? ib - 3 : ib + 2;
-    }
-  } else {
   for (int kt = 0; kt < nk; ++kt) {
     const unsigned char* st = smem + (kt & 1) * STAGE;
-#ifdef VL_EXP_NO_DMA
-    const bool n1 = false, n2 = false;
-#else
     const bool n1 = kt + 1 < nk, n2 = kt + 2 < nk;
-#endif
     // phase 0: quadrant (0,0)
     G3_READ_B(st, 0, fb0);
     __builtin_amdgcn_sched_barrier(0);
@@ -798,7 +647,6 @@ __global__ __launch_bounds__(512) void gemm3_kernel(GemmArgs p) {
     if (n2) G3_ISSUE(2, kt + 2);
     G3_WAIT(n2);
     G3_MFMA(1, 0, fb0);
-  }
   }
   if (!late) __builtin_amdgcn_s_barrier();  // matches the stagger barrier
   // the finished tile's coordinates for the epilogue; then (PERSIST) the next tile's DMA prologue goes out first
@@ -964,11 +812,6 @@ __global__ __launch_bounds__(512) void gemm3_kernel(GemmArgs p) {
 #undef G3_MFMA
 #undef G3_PROLOGUE_ISSUE
 #undef G3_PROLOGUE_WAIT
-#undef G5_ISSUE
-#undef G5_WAIT_YOUNGER
-#undef G5_WAIT
-#undef G5_READ_A
-#undef G5_READ_B
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -979,15 +822,6 @@ __global__ __launch_bounds__(512) void gemm3_kernel(GemmArgs p) {
 // fragment).  32-byte column blocks are XOR-swizzled with h(k) = (k&3) | ((k>>3)&1)<<2 (applied on the DMA source
 // address, undone by the reads) so that the 8 k-rows a 32-lane half touches hit 8 different 32-byte bank groups.
 // ---------------------------------------------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* p0, const unsigned char* p1) {
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p0);
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p1);
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, v);
-}
-
 template <int BN>
 __global__ __launch_bounds__(1024, 4) void gemm2_tn_kernel(GemmArgs p) {
   constexpr int BM2 = 256, NT = BN / 64, MT = 4, NWAVES = 16;
@@ -1004,9 +838,7 @@ __global__ __launch_bounds__(1024, 4) void gemm2_tn_kernel(GemmArgs p) {
   // HBM by one XCD's L2 only, instead of by every XCD that happens to host one of its tiles.
   const int tiles = p.tiles_m * p.tiles_n;
   const int nwg = tiles * p.splits;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int swz = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int swz = xcd_tile(blockIdx.x, nwg);
   const int split = swz / tiles, tile = swz - split * tiles;
   const int tm = tile / p.tiles_n, tn = tile - tm * p.tiles_n;
   const int row0 = tm * BM2, col0 = tn * BN;
@@ -1105,11 +937,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs p) {
   const int wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
 
-  // XCD-aware (bijective) remap of the linear block id -> (tile_m, tile_n)
-  const int nwg = p.tiles_m * p.tiles_n;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-  const int swz = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+  const int swz = xcd_tile(blockIdx.x, p.tiles_m * p.tiles_n);  // linear block id -> (tile_m, tile_n)
   const int tm = swz / p.tiles_n, tn = swz - tm * p.tiles_n;
   const int row0 = tm * BM, col0 = tn * BN;
 
@@ -1371,54 +1199,26 @@ int launch_small(const GemmArgs& a, float* ws, hipStream_t stream) {
 template <int NSPLIT, int EPI>
 int launch(const GemmArgs& a, hipStream_t stream, int splits = 1) {
   const size_t lds = (NSPLIT == 3 ? 4 : 2) * TILE_BYTES;
-  static bool attr_set = false;  // per instantiation; idempotent, so a race only repeats the call
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_kernel<NSPLIT, EPI>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return vl_set_error(-3, "vl_gemm_nt: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((gemm_nt_kernel<NSPLIT, EPI>), dim3(a.tiles_m * a.tiles_n, splits), dim3(256), lds, stream, a);
-  VL_CHECK_LAUNCH("vl_gemm_nt");
-  return 0;
+  return launch_dyn_lds<&gemm_nt_kernel<NSPLIT, EPI>>("vl_gemm_nt", dim3(a.tiles_m * a.tiles_n, splits), dim3(256), lds, stream, a);
 }
 
 template <int NSPLIT, int EPI, int BN, int WM>
 int launch2w(GemmArgs a, hipStream_t stream, int splits) {
   const size_t lds = 2 * ((256 + BN) / 8) * 1024;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm2_kernel<NSPLIT, EPI, BN, WM>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return vl_set_error(-3, "vl_gemm_nt: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
   a.tiles_m = (a.M + 255) / 256;
   a.tiles_n = (a.N + BN - 1) / BN;
-  hipLaunchKernelGGL((gemm2_kernel<NSPLIT, EPI, BN, WM>), dim3(a.tiles_m * a.tiles_n, splits), dim3(WM * 256), lds,
-                     stream, a);
-  VL_CHECK_LAUNCH("vl_gemm_nt(fast)");
-  return 0;
+  return launch_dyn_lds<&gemm2_kernel<NSPLIT, EPI, BN, WM>>("vl_gemm_nt(fast)", dim3(a.tiles_m * a.tiles_n, splits), dim3(WM * 256),
+                                                           lds, stream, a);
 }
 thread_local int tl_cs_rows = 0;  // scratch of one vl_gemm_nt_ex call (reported through VL_GX_COLSUM_ROWS)
 template <int NSPLIT, int EPI, int CFG, bool PERSIST>
 int launch3p(const GemmArgs& a, int grid, size_t lds, hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm3_kernel<NSPLIT, EPI, CFG, PERSIST>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return vl_set_error(-3, "vl_gemm_nt: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((gemm3_kernel<NSPLIT, EPI, CFG, PERSIST>), dim3(grid), dim3(512), lds, stream, a);
-  VL_CHECK_LAUNCH("vl_gemm_nt(ping-pong)");
-  return 0;
+  return launch_dyn_lds<&gemm3_kernel<NSPLIT, EPI, CFG, PERSIST>>("vl_gemm_nt(ping-pong)", dim3(grid), dim3(512), lds, stream, a);
 }
 template <int NSPLIT, int EPI, int CFG>
 int launch3(GemmArgs a, hipStream_t stream) {
   constexpr int BMT = CFG == 2 ? 224 : 256, BNT = CFG == 1 ? 192 : 256;
-  // two K-tiles of both operands, or (VL_GEMM_RING == 5) five half-tile slots per operand: 160 KB at 256 x 256, all of a CU's LDS
-  const size_t lds = VL_GEMM_RING == 5 ? 5 * (128 + BNT / 2) * 128 : 2 * (BMT + BNT) * 128;
+  const size_t lds = 2 * (BMT + BNT) * 128;  // two K-tiles of both operands
   a.tiles_m = (a.M + BMT - 1) / BMT;
   a.tiles_n = (a.N + BNT - 1) / BNT;
   tl_cs_rows = a.tiles_m * 2 * (CFG == 1 ? 4 : 2);  // column-sum partial rows this configuration writes
@@ -1433,11 +1233,6 @@ int launch3(GemmArgs a, hipStream_t stream) {
   }
   return launch3p<NSPLIT, EPI, CFG, false>(a, tiles, lds, stream);
 }
-template <int NSPLIT, int EPI, int BN>
-int launch2(const GemmArgs& a, hipStream_t stream, int splits) {
-  return launch2w<NSPLIT, EPI, BN, 4>(a, stream, splits);
-}
-
 
 // BN for the fast path: fewest "rounds x tile width" over the 256 CUs (one 512-thread workgroup per CU)
 inline int pick_bn(int64_t M, int64_t N, int splits, int tile) {
@@ -1487,9 +1282,9 @@ int launch_any(const GemmArgs& a, hipStream_t s, int splits = 1) {
   if (a.cs) return vl_set_error(-2, "vl_gemm_nt_ex: column sums are produced by the ping-pong kernel only (see vl_gemm_nt_path)");
   if (fast_ok(a.M, a.K, a.k_len, NSPLIT, a.tile)) {
     switch (pick_bn(a.M, a.N, splits, a.tile)) {
-      case 256: return launch2<NSPLIT, EPI, 256>(a, s, splits);
-      case 192: return launch2<NSPLIT, EPI, 192>(a, s, splits);
-      default: return launch2<NSPLIT, EPI, 128>(a, s, splits);
+      case 256: return launch2w<NSPLIT, EPI, 256, 4>(a, s, splits);
+      case 192: return launch2w<NSPLIT, EPI, 192, 4>(a, s, splits);
+      default: return launch2w<NSPLIT, EPI, 128, 4>(a, s, splits);
     }
   }
   return launch<NSPLIT, EPI>(a, s, splits);
@@ -1508,6 +1303,16 @@ int dispatch_epi(int epi, const GemmArgs& a, hipStream_t s) {
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// second launch of the split-K entry points: out32[M * N] = the sum of the `splits` slabs of ws, in slab order
+int launch_splitk_reduce(const char* what, const float* ws, int splits, int64_t mn, float* out32, hipStream_t s) {
+  const long n4 = (long)(mn / 4);
+  long g = (n4 + 255) / 256;
+  if (g > 2048) g = 2048;
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)g), dim3(256), 0, s, ws, splits, n4, out32);
+  VL_CHECK_LAUNCH(what);
+  return 0;
+}
 
 }  // namespace
 
@@ -1645,12 +1450,7 @@ extern "C" int vl_gemm_nt_splitk(const void* a_hi, int64_t lda, const void* b_hi
   }
   a.out32 = ws; a.slab_stride = M * N;
   if (int rc = launch_any<1, VL_EPI_F32>(a, s, eff)) return rc;
-  const long n4 = (long)(M * N / 4);
-  long g = (n4 + 255) / 256;
-  if (g > 2048) g = 2048;
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)g), dim3(256), 0, s, ws, eff, n4, out32);
-  VL_CHECK_LAUNCH("vl_gemm_nt_splitk(reduce)");
-  return 0;
+  return launch_splitk_reduce("vl_gemm_nt_splitk(reduce)", ws, eff, M * N, out32, s);
 }
 
 // dW[M,N] = A^T B with A [K, M] (lda), B [K, N] (ldb) row-major bf16 (the activations as they sit in HBM), K = the
@@ -1676,24 +1476,11 @@ int tn_splitk_impl(const void* a, int64_t lda, const void* b, int64_t ldb, int64
   g.splits = eff;
   hipStream_t s = (hipStream_t)stream;
   const size_t lds = 2 * (size_t)(64 * 512 + 64 * bn * 2);
-  hipError_t e = bn == 256 ? hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm2_tn_kernel<256>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                           : hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm2_tn_kernel<128>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return vl_set_error(-3, "vl_gemm_tn_splitk: hipFuncSetAttribute: %s", hipGetErrorString(e));
-  if (bn == 256)
-    hipLaunchKernelGGL((gemm2_tn_kernel<256>), dim3(g.tiles_m * g.tiles_n * eff), dim3(1024), lds, s, g);
-  else
-    hipLaunchKernelGGL((gemm2_tn_kernel<128>), dim3(g.tiles_m * g.tiles_n * eff), dim3(1024), lds, s, g);
-  VL_CHECK_LAUNCH("vl_gemm_tn_splitk");
-  if (!direct) {
-    const long n4 = (long)(M * N / 4);
-    long gr = (n4 + 255) / 256;
-    if (gr > 2048) gr = 2048;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)gr), dim3(256), 0, s, ws, eff, n4, out32);
-    VL_CHECK_LAUNCH("vl_gemm_tn_splitk(reduce)");
-  }
-  return 0;
+  const dim3 grid(g.tiles_m * g.tiles_n * eff);
+  if (int rc = bn == 256 ? launch_dyn_lds<&gemm2_tn_kernel<256>>("vl_gemm_tn_splitk", grid, dim3(1024), lds, s, g)
+                         : launch_dyn_lds<&gemm2_tn_kernel<128>>("vl_gemm_tn_splitk", grid, dim3(1024), lds, s, g))
+    return rc;
+  return direct ? 0 : launch_splitk_reduce("vl_gemm_tn_splitk(reduce)", ws, eff, M * N, out32, s);
 }
 inline bool tn_shape_ok(const void* a, int64_t lda, const void* b, int64_t ldb, int64_t M, int64_t N, int64_t K,
                         const void* ws) {

@@ -66,3 +66,20 @@ def test_dw_kernel_main_loop_has_no_compiler_inserted_dma_drain(tmp_path):
         else:
             meta = "\n".join(body)
             assert "scratch_" not in meta, f"{name}: register spills"
+
+
+def test_kernel_sources_carry_no_wrong_result_build_switches():
+    """The timing experiments that computed wrong results on purpose are finished and on record (profiles/r03_ab_log.txt):
+    no source under csrc/ may bring back a VL_EXP* switch, i.e. a way to build a library that silently computes garbage."""
+    offenders = []
+    for root, dirs, names in os.walk(CSRC):
+        dirs[:] = [d for d in dirs if not d.startswith("ab_")]  # A/B variant builds of other commits: build products
+        for name in sorted(names):
+            if name.endswith((".o", ".so", ".a")):  # build products
+                continue
+            path = os.path.join(root, name)
+            text = open(path, encoding="utf-8", errors="replace").read()
+            for lineno, line in enumerate(text.split("\n"), 1):
+                if "VL_EXP" in line or "WRONG RESULTS" in line.upper():
+                    offenders.append("%s:%d: %s" % (os.path.relpath(path, CSRC), lineno, line.strip()))
+    assert not offenders, "\n".join(offenders)

@@ -9,10 +9,25 @@ import torch
 sys.path.insert(0, ".")
 from clg_vqa_amd import ops  # noqa: E402
 from clg_vqa_amd.ops import BF16, EPI_BF16, EPI_SPLIT  # noqa: E402
-from tools.gemm_exp import med  # noqa: E402
 
 DEV = "cuda"
 M, N = 14336, 2304
+
+
+def med(fn, n=10):
+    """median of n timings in us, caches flushed by a 512 MB fill between launches"""
+    filler = torch.empty(512 << 20, dtype=torch.uint8, device=DEV)
+    ts = []
+    for _ in range(n):
+        filler.zero_()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        ts.append(e0.elapsed_time(e1) * 1e3)
+    ts.sort()
+    return ts[len(ts) // 2]
 
 
 def main():
