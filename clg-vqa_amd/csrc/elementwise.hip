@@ -467,9 +467,11 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
   float gs = gscale_ptr ? *gscale_ptr : gscale_const;
   if (sumsq_ptr) {
     // clip_grad_norm_ (train_task.py:330) on the device: ||g|| of the averaged gradient = sqrt(sum g^2) * post;
-    // coefficient min(1, max_norm / (||g|| + 1e-6)), times the 1/world factor `post` of the all-reduce
+    // coefficient min(1, max_norm / (||g|| + 1e-6)), times the 1/world factor `post` of the all-reduce.  A NaN norm stays
+    // NaN, as in torch.clamp (fminf would turn it into 1): every parameter with a gradient becomes NaN, as in the reference
     const float norm = sqrtf(*sumsq_ptr) * post;
-    gs = fminf(max_norm / (norm + 1e-6f), 1.0f) * post;
+    const float q = max_norm / (norm + 1e-6f);
+    gs = (q > 1.0f ? 1.0f : q) * post;
   }
   if (sumsq_next && blockIdx.x == 0 && threadIdx.x == 0) *sumsq_next = 0.f;  // the NEXT step's accumulator (nobody reads it now)
   const float c1 = 1.f - b1, c2 = 1.f - b2;

@@ -537,7 +537,8 @@ int vl_gqa_loss(const float* logits, const float* target, const float* distances
  * train_task.py:274).  `step` = 1-based optimizer step.  Also zeroes the gradient when zero_grad != 0.
  * sumsq_dev (may be NULL): device scalar sum(g^2) (vl_sumsq): the kernel then computes the clip_grad_norm_ coefficient
  * itself, grad scale = min(1, max_norm / (sqrt(sumsq) * post + 1e-6)) * post (post = 1/world_size of the all-reduce),
- * overriding grad_scale_dev / grad_scale; sumsq_next (may be NULL) = ANOTHER device scalar that is set to 0 (the next
+ * overriding grad_scale_dev / grad_scale (a NaN sumsq gives a NaN scale, as torch.clamp does: every parameter with a
+ * gradient becomes NaN); sumsq_next (may be NULL) = ANOTHER device scalar that is set to 0 (the next
  * step's accumulator: two alternate, so no separate fill launch is needed).
  * row_flags (may be NULL): per-row "has ever received a gradient" bytes for the table occupying arena elements
  * [flag_begin, flag_begin + flag_rows*flag_row_len): rows with flag 0 have g = m = v = 0, so only p *= (1 - lr*wd)
@@ -547,6 +548,7 @@ int vl_gqa_loss(const float* logits, const float* target, const float* distances
  * seg_step (may be NULL): DEVICE array of nseg 1-based per-segment step counts for the bias correction -- the reference
  * optimizer keeps state['step'] per parameter and advances it only on steps where that parameter has a gradient; NULL =
  * every segment is at `step`.
+ * beta1 / beta2 are taken as the floats they arrive as: the moments use b = fl(beta) and 1.f - b, the bias correction the same b.
  * ------------------------------------------------------------------------------------------------------------ */
 int vl_adamw(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const int64_t* seg_end,
              const float* seg_lr, const float* seg_wd, int64_t nseg, float beta1, float beta2, float eps,

@@ -1283,3 +1283,152 @@ def test_dw_grouped_rowmajor_matches_fp64_and_the_kmajor_path(K):
     ops.dw_grouped_rowmajor([(odd_a, odd_b, o3, None, 320, 200, c3)], K)
     torch.testing.assert_close(o3.double(), odd_a.double().t() @ odd_b.double(), rtol=2e-5, atol=tol)
     torch.testing.assert_close(c3[0].double(), odd_a.double().sum(0), rtol=1e-5, atol=1e-3 * math.sqrt(K / 64))
+
+
+# ---- entry points of the training path that only whole-model tests used to reach ----------------------------------------
+_FILL16 = -1  # int16 0xFFFF: a bf16 NaN
+
+
+def _filled_bf16(*shape):
+    return torch.full(shape, _FILL16, dtype=torch.int16, device=DEV).view(BF16)
+
+
+def test_weight_prep_multi_descriptor_table():
+    """vl_weight_prep_multi: seven weights behind one device table of [w32, mask32, w_hi, w_lo, wt_hi, N, K, ldw, ldt,
+    first_tile], destinations packed the way the engine packs them (row slices of a [*, K] buffer, column slices of a
+    [K, *] buffer), NaN-filled beforehand: the written rectangles hold the bits of vl_weight_prep on each weight alone,
+    everything else still holds the fill -- in particular around the last tile of one descriptor and the first of the next."""
+    # (N, K, mask, w_lo, wt_hi)
+    specs = [(64, 64, True, True, True),      # exactly one tile, vector path
+             (192, 128, True, True, True),    # vector path, shares its packed buffers with the (64, 128) weight
+             (130, 72, True, True, True),     # ragged in both directions: scalar path
+             (66, 70, True, True, True),      # K not a multiple of 4
+             (128, 64, False, True, True),    # null mask32
+             (64, 128, True, False, True),    # null w_lo
+             (64, 64, True, True, False)]     # null wt_hi
+    gen = torch.Generator().manual_seed(77)
+    rows_of, bufs = {}, {}
+    for N, K, _, _, _ in specs:
+        rows_of[K] = rows_of.get(K, 0) + N
+    for K, rows in rows_of.items():  # per K: hi / lo [8 + rows + 8, K] and wt [K, 8 + rows + 8], for both launch forms
+        bufs[K] = [dict(hi=_filled_bf16(rows + 16, K), lo=_filled_bf16(rows + 16, K), wt=_filled_bf16(K, rows + 16))
+                   for _ in range(2)]
+    written = {K: dict(hi=torch.zeros(rows + 16, K, dtype=torch.bool), lo=torch.zeros(rows + 16, K, dtype=torch.bool),
+                       wt=torch.zeros(K, rows + 16, dtype=torch.bool)) for K, rows in rows_of.items()}
+    at = {K: 8 for K in rows_of}
+    table, keep, views, tiles = [], [], [], 0
+    for N, K, has_mask, has_lo, has_wt in specs:
+        w = torch.randn(N, K, generator=gen).to(DEV)
+        mask = (torch.rand(N, K, generator=gen) < 0.6).float().to(DEV) if has_mask else None
+        r0 = at[K]
+        at[K] += N
+        sl = []
+        for b in bufs[K]:
+            sl.append((b["hi"][r0:r0 + N], b["lo"][r0:r0 + N] if has_lo else None, b["wt"][:, r0:r0 + N] if has_wt else None))
+        written[K]["hi"][r0:r0 + N] = True
+        written[K]["lo"][r0:r0 + N] = has_lo
+        written[K]["wt"][:, r0:r0 + N] = has_wt
+        hi, lo, wt = sl[0]
+        table.append([w.data_ptr(), mask.data_ptr() if has_mask else 0, hi.data_ptr(), lo.data_ptr() if has_lo else 0,
+                      wt.data_ptr() if has_wt else 0, N, K, K, rows_of[K] + 16, tiles])
+        tiles += ((N + 63) // 64) * ((K + 63) // 64)
+        ops.weight_prep(w, mask, *sl[1])   # the same weight alone, into the second set of buffers
+        keep.append((w, mask))
+        views.append((w if mask is None else w * mask, hi, lo, wt))
+    assert tiles == 22 and [t[9] for t in table] == [0, 1, 7, 13, 17, 19, 21]
+    tab = torch.tensor(table, dtype=torch.int64).to(DEV)
+    ops.weight_prep_multi(tab, len(specs), tiles)
+    for wm, hi, lo, wt in views:
+        assert torch.equal(hi, wm.to(BF16))
+        if lo is not None:
+            assert (hi.float() + lo.float() - wm).abs().max().item() <= 2.0 ** -16 * wm.abs().max().item()
+        if wt is not None:
+            assert torch.equal(wt, hi.t())
+    for K in rows_of:
+        for name in ("hi", "lo", "wt"):
+            multi, single = (b[name].view(torch.int16).cpu() for b in bufs[K])
+            assert torch.equal(multi, single), (K, name)
+            assert (multi[~written[K][name]] == _FILL16).all(), (K, name)
+            assert not (multi[written[K][name]] == _FILL16).any(), (K, name)  # (no bf16 of a finite product is 0xFFFF)
+
+
+@pytest.mark.parametrize("M_a,M_b,H", [(333, 47, 768), (5, 2000, 128), (1, 1, 256)])
+def test_ln_bwd_reduce2_equals_two_reductions_and_fp64_column_sums(M_a, M_b, H):
+    sets = []
+    for k, M in enumerate((M_a, M_b)):
+        y, gamma, beta = _rand(M, H, seed=90 + k), 1 + 0.1 * _rand(H, seed=92 + k), 0.1 * _rand(H, seed=94 + k)
+        dy = _rand(M, H, seed=96 + k)
+        z, out = y.clone(), torch.empty(M, H, device=DEV)
+        mean, rstd = torch.empty(M, device=DEV), torch.empty(M, device=DEV)
+        ops.ln_fwd(z, None, None, gamma, beta, 1e-5, out, None, None, mean, rstd, M, H)
+        ws = ops.ln_bwd_ws(M, H, DEV)
+        dz = torch.empty(M, H, device=DEV)
+        ops.ln_bwd(dy, z, mean, rstd, gamma, dz, None, None, None, None, None, ws, M, H)
+        single = [torch.full((H,), float("nan"), device=DEV) for _ in range(3)]
+        ops.ln_bwd_reduce(ws, M, H, *single)
+        zr = y.double().requires_grad_(True)
+        g64, b64 = gamma.double().requires_grad_(True), beta.double().requires_grad_(True)
+        u = zr.mean(-1, keepdim=True)
+        s = (zr - u).pow(2).mean(-1, keepdim=True)
+        (g64 * ((zr - u) / torch.sqrt(s + 1e-5)) + b64).backward(dy.double())
+        sets.append((ws, M, single, (g64.grad, b64.grad, zr.grad.sum(0))))
+    (ws_a, _, single_a, ref_a), (ws_b, _, single_b, ref_b) = sets
+    # accumulate = False: a NaN pre-fill is overwritten, with the bits of the two separate reductions
+    outs_a = [torch.full((H,), float("nan"), device=DEV) for _ in range(3)]
+    outs_b = [torch.full((H,), float("nan"), device=DEV) for _ in range(3)]
+    ops.ln_bwd_reduce2(ws_a, M_a, outs_a, ws_b, M_b, outs_b, H)
+    for got, one, ref in zip(outs_a + outs_b, single_a + single_b, ref_a + ref_b):
+        assert torch.equal(got, one)
+        torch.testing.assert_close(got.double(), ref, rtol=1e-4, atol=1e-4)  # (test_layernorm_forward_backward's bounds)
+    # accumulate = True: pre-fill plus the same sums (one fp32 addition per column)
+    pre_a = [_rand(H, seed=100 + k) for k in range(3)]
+    pre_b = [_rand(H, seed=103 + k) for k in range(3)]
+    acc_a, acc_b = [t.clone() for t in pre_a], [t.clone() for t in pre_b]
+    ops.ln_bwd_reduce2(ws_a, M_a, acc_a, ws_b, M_b, acc_b, H, accumulate=True)
+    for got, pre, one in zip(acc_a + acc_b, pre_a + pre_b, single_a + single_b):
+        assert torch.equal(got, pre + one)
+
+
+@pytest.mark.parametrize("R,H", [(1, 4), (7, 260), (1030, 768)])
+def test_embed_gather_and_scatter_add(R, H):
+    """vl_embed_gather_fwd / vl_embed_scatter_add: the M3P text embedding and the sparse word-gradient exchange."""
+    vocab, pad = 50, 1
+    gen = torch.Generator().manual_seed(R + H)
+    table = _rand(vocab, H, seed=110)
+    ids = torch.randint(0, 9, (R,), generator=gen).to(DEV)  # repeated ids
+    out = torch.full((R, H), float("nan"), device=DEV)
+    ops.embed_gather_fwd(ids, table, out, R, H)
+    assert torch.equal(out, table[ids])
+    # scatter-add: 12 distinct rows, every one hit by many float atomics; pad rows and empty (-1) slots contribute nothing
+    rows = torch.tensor([0, 2, 3, 5, 8, 13, 21, 34, 40, 44, 47, 49])
+    ids = rows[torch.randint(0, 12, (R,), generator=gen)]
+    if R >= 7:
+        ids[2], ids[R - 2] = pad, pad
+        ids[5], ids[R - 1] = -1, -1
+    keep = (ids != pad) & (ids >= 0)
+    assert keep.any()
+    ids = ids.to(DEV)
+    dz = _rand(R, H, seed=111)
+    base = _rand(vocab, H, seed=112)
+    ref = base.double().cpu().index_add_(0, ids.cpu()[keep], dz.double().cpu()[keep])
+    touched = torch.zeros(vocab, dtype=torch.uint8)
+    touched[ids.cpu()[keep]] = 1
+    tol = 2e-6 * math.sqrt(R) * dz.abs().max().item()  # arrival order varies (the deterministic-scatter test's form)
+    for with_flags in (True, False):
+        dtable = base.clone()
+        flags = torch.zeros(vocab, dtype=torch.uint8, device=DEV) if with_flags else None
+        ops.embed_scatter_add(ids, dz, dtable, R, H, pad, row_flags=flags)
+        torch.testing.assert_close(dtable.double().cpu(), ref, rtol=1e-6, atol=tol)
+        untouched = touched == 0
+        assert torch.equal(dtable.cpu()[untouched], base.cpu()[untouched])  # pad row included
+        if with_flags:
+            assert torch.equal(flags.cpu(), touched)
+
+
+@pytest.mark.parametrize("nbytes", [1, 4097, (8 << 20) + 3])
+def test_memset_zero_touches_only_its_range(nbytes):
+    off = 5
+    buf = torch.full((off + nbytes + 11,), 0xFF, dtype=torch.uint8, device=DEV)
+    ops.memset_zero(buf[off:off + nbytes])
+    assert (buf[:off] == 0xFF).all() and (buf[off + nbytes:] == 0xFF).all()
+    assert not buf[off:off + nbytes].any()
