@@ -78,6 +78,7 @@ _SIGS = {
     "vl_loc_linear_fwd": (c_int, [P, P, P, P, c_int64, c_int64, c_int64, P]),
     "vl_loc_linear_bwd": (c_int, [P, P, P, P, c_int64, c_int64, c_int64, P, P]),
     "vl_loc_bwd_ws_floats": (c_int64, [c_int64, c_int64]),
+    "vl_loc_linear_bwd_input": (c_int, [P, P, P, c_int64, c_int64, c_int64, P]),
     "vl_scatter_det_ws_bytes": (c_int64, [c_int64, c_int64, c_int64]),
     "vl_scatter_add_det": (c_int, [P, c_int64, P, c_int64, c_int64, P, c_int64, P]),
     "vl_adamw": (c_int, [P, P, P, P, c_int64, P, P, P, c_int64, c_float, c_float, c_float, c_int64, P, c_int, c_float,

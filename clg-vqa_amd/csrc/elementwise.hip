@@ -431,6 +431,58 @@ __global__ __launch_bounds__(256) void loc_bwd_reduce_kernel(const float* __rest
     else db[c] += t;
   }
 }
+// dloc[r][l] = sum_c dy[r][c] w[c][l]: the gradient of the projection with respect to the box coordinates.  dy is the only
+// large operand (R x H floats against H x L): a workgroup stages w once in LDS, transposed to [l][c] so that a lane reads the
+// weights of its 4 columns with one 16-byte LDS load, and walks LI_ROWS rows; a wave owns whole rows, 4 at a time (4
+// independent 16-byte loads of dy in flight per lane), lane q adds the column quads q, q + 64, ... in ascending order and
+// the 64 partial sums of a row go through the xor butterfly of wave_sum: one fixed order, no atomics.
+#define LI_ROWS 32
+__global__ __launch_bounds__(256) void loc_bwd_input_kernel(const float* __restrict__ dy, const float* __restrict__ w,
+                                                            float* __restrict__ dloc, long R, int L, int H) {
+  extern __shared__ __attribute__((aligned(16))) float wt[];  // [L][H]
+  for (int i = threadIdx.x; i < H * L; i += 256) {
+    const int c = i / L;
+    wt[(i - c * L) * H + c] = w[i];
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int cq = H >> 2;  // column quads per row (H % 4 == 0, checked by the host)
+  const long r0 = (long)blockIdx.x * LI_ROWS + wave * (LI_ROWS / 4);
+#pragma unroll 1
+  for (int i0 = 0; i0 < LI_ROWS / 4; i0 += 4) {
+    const long r = r0 + i0;
+    if (r >= R) break;
+    float acc[4][8];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int l = 0; l < 8; ++l) acc[i][l] = 0.f;
+    for (int q = lane; q < cq; q += 64) {
+      float4 g[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        g[i] = r + i < R ? *reinterpret_cast<const float4*>(dy + (r + i) * H + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int l = 0; l < 8; ++l) {
+        if (l < L) {
+          const float4 ww = *reinterpret_cast<const float4*>(wt + l * H + 4 * q);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) acc[i][l] += (g[i].x * ww.x + g[i].y * ww.y) + (g[i].z * ww.z + g[i].w * ww.w);
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+      for (int l = 0; l < 8; ++l) {
+        if (l < L) {
+          const float t = wave_sum(acc[i][l]);
+          if (lane == l && r + i < R) dloc[(r + i) * L + l] = t;
+        }
+      }
+    }
+  }
+}
 
 // ---- fused AdamW over a flat arena ---------------------------------------------------------------------------
 // pytorch_transformers.optimization.AdamW semantics (un-vendored dependency of the reference; call site
@@ -737,6 +789,18 @@ extern "C" int vl_loc_linear_bwd(const float* loc, const float* dy32, float* dw,
     hipLaunchKernelGGL(loc_bwd_reduce_kernel, dim3((unsigned)((H + 63) / 64), (unsigned)(L + 1)), dim3(256), 0, (hipStream_t)stream,
                        ws, dw, db, (int)nrb, (int)L, (int)H);
   VL_CHECK_LAUNCH("vl_loc_linear_bwd");
+  return 0;
+}
+extern "C" int vl_loc_linear_bwd_input(const float* dy32, const float* w, float* dloc32, int64_t R, int64_t L, int64_t H,
+                                       void* stream) {
+  VL_CHECK_ARG(dy32 && w && dloc32, "vl_loc_linear_bwd_input: null pointer");
+  VL_CHECK_ARG(R > 0 && R < (1LL << 31) && L > 0 && L <= 8 && H > 0 && (H & 3) == 0 && H <= 2048,
+               "vl_loc_linear_bwd_input: bad shape R=%lld L=%lld H=%lld (L <= 8, H a multiple of 4, at most 2048)", (long long)R,
+               (long long)L, (long long)H);
+  VL_CHECK_ARG(((uintptr_t)dy32 & 15) == 0, "vl_loc_linear_bwd_input: dy32 must be 16-byte aligned");
+  hipLaunchKernelGGL(loc_bwd_input_kernel, dim3((unsigned)((R + LI_ROWS - 1) / LI_ROWS)), dim3(256),
+                     (size_t)(L * H) * sizeof(float), (hipStream_t)stream, dy32, w, dloc32, (long)R, (int)L, (int)H);
+  VL_CHECK_LAUNCH("vl_loc_linear_bwd_input");
   return 0;
 }
 

@@ -176,6 +176,40 @@ def dw_gemm(dy16, x16, M, N, K, mask=None):
     return dW if mask is None else ops.mask_mul(dW, mask, dW)
 
 
+def check_input_grads(H, feats, locs, want_feats, want_locs):
+    """Refuse in forward what the two input-gradient products cannot take: a gradient that was asked for is never left
+    as a silent None."""
+    BV, F, L = feats.shape[0] * feats.shape[1], feats.shape[2], locs.shape[2]
+    if want_feats and not (0 < BV < (1 << 30) and 0 < F < (1 << 30)):
+        raise ValueError("clg_vqa_amd: no gradient for the region features of this shape (boxes %d x features %d: the GEMM "
+                         "takes dimensions below 2^30)" % (BV, F))
+    if want_locs and (L > 8 or H > 2048):
+        raise ValueError("clg_vqa_amd: no gradient for box locations with more than 8 coordinates or a hidden size above "
+                         "2048 (got %d coordinates, hidden %d)" % (L, H))
+
+
+def input_grad_feats(dimg16, w_hi):
+    """d(features) [BV,F] fp32 = d(img) [BV,H] . W_img [H,F]: one single-pass bf16 product like every other product of
+    backward.  `w_hi` is the prepared bf16 weight the forward pass used (under SFT the masked one); its transposed image
+    is made here, on demand, so that a step without input gradients never pays for it."""
+    BV, H = dimg16.shape
+    F = w_hi.shape[1]
+    wT = ops._tmp(torch.empty(F, H, dtype=BF16, device=dimg16.device))
+    ops.transpose_bf16(w_hi, wT, H, F)
+    dfeats = torch.empty(BV, F, dtype=torch.float32, device=dimg16.device)
+    ops.gemm_nt(dimg16, None, wT, None, BV, F, H, 1, EPI_F32, out32=dfeats)
+    return dfeats
+
+
+def input_grad_locs(dloc32, w_loc):
+    """d(box locations) [BV,L] fp32 = d(loc) [BV,H] . W_loc [H,L] (fp32, csrc/elementwise.hip)."""
+    BV, H = dloc32.shape
+    L = w_loc.shape[1]
+    dlocs = torch.empty(BV, L, dtype=torch.float32, device=dloc32.device)
+    ops.loc_linear_bwd_input(dloc32, w_loc, dlocs, BV, L, H)
+    return dlocs
+
+
 class LayerSpec(object):
     """Leaf modules of one post-LN transformer layer (UC2: attention sub-layer 2l + feed-forward sub-layer 2l+1;
     M3P: attentions[l] / layer_norm1[l] / ffns[l] / layer_norm2[l])."""
@@ -887,8 +921,9 @@ class UC2Engine(EngineBase):
         return self.stack.forward(ar, pw["layers"], p_hid, p_att, seed0, taps=taps), sv
 
     # ---- backward ------------------------------------------------------------------------------------------------
-    def backward(self, sv, dx):
-        """dx: [B,S,H] fp32 gradient of the trunk output.  Returns grads in ``param_list`` order."""
+    def backward(self, sv, dx, want_feats=False, want_locs=False):
+        """dx: [B,S,H] fp32 gradient of the trunk output.  Returns (grads in ``param_list`` order, d(features) [B,V,F] or
+        None, d(box locations) [B,V,L] or None): the input gradients only when asked for."""
         cfg = self.model.config
         emb = self.model.bert.embeddings
         B, T, V, F, L, S = sv["B"], sv["T"], sv["V"], sv["F"], sv["L"], sv["S"]
@@ -924,6 +959,8 @@ class UC2Engine(EngineBase):
         dWl = torch.zeros_like(emb.image_location_embeddings.weight)
         dbl = torch.zeros_like(emb.image_location_embeddings.bias)
         ops.loc_linear_bwd(sv["locs"], dloc32, dWl, dbl, BV, L, H)
+        dfeats = input_grad_feats(dimg16, pw["img"].hi).view(B, V, F) if want_feats else None
+        dlocs = input_grad_locs(dloc32, emb.image_location_embeddings.weight.detach()).view(B, V, L) if want_locs else None
         # text rows
         dz_t, dg_e, db_e = f32(BT, H), f32(H), f32(H)
         ops.ln_bwd(dy, sv["z_t"], sv["mean_t"], sv["rstd_t"], emb.LayerNorm.weight.detach(), dz_t, None, None, dg_e,
@@ -939,7 +976,7 @@ class UC2Engine(EngineBase):
                  db_l, dg_v, db_v]
         for lg in layer_grads:
             grads += lg
-        return grads
+        return grads, dfeats, dlocs
 
 
 class TrunkFunction(torch.autograd.Function):
@@ -948,12 +985,14 @@ class TrunkFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, engine, training, ids, feats, locs, seg, tmask, imask, *params):
+        # whether a backward can follow: the caller's grad mode (inside autograd.Function.forward it is always off,
+        # and ctx.needs_input_grad ignores torch.no_grad()) and whether any parameter or input wants a gradient
+        need_grad = engine.grad_mode and any(ctx.needs_input_grad)
+        if need_grad:
+            check_input_grads(engine.H, feats, locs, ctx.needs_input_grad[3], ctx.needs_input_grad[4])
         ops.set_stream(torch.cuda.current_stream().cuda_stream)  # one stream lookup for all launches of the pass
         try:
-            # whether a backward can follow: the caller's grad mode (inside autograd.Function.forward it is always off,
-            # and ctx.needs_input_grad ignores torch.no_grad()) and whether any parameter wants a gradient
-            out, sv = engine.forward(ids, feats, locs, seg, tmask, imask, training,
-                                     need_grad=engine.grad_mode and any(ctx.needs_input_grad))
+            out, sv = engine.forward(ids, feats, locs, seg, tmask, imask, training, need_grad=need_grad)
         finally:
             ops.set_stream(None)
         ctx.engine = engine
@@ -968,14 +1007,15 @@ class TrunkFunction(torch.autograd.Function):
                                "(retain_graph / double backward are not supported by the native trunk)")
         ops.set_stream(torch.cuda.current_stream().cuda_stream)
         try:
-            grads = ctx.engine.backward(ctx.sv, dx)
+            grads, dfeats, dlocs = ctx.engine.backward(ctx.sv, dx, want_feats=ctx.needs_input_grad[3],
+                                                       want_locs=ctx.needs_input_grad[4])
         finally:
             ops.set_stream(None)
             ctx.engine.stack.join()
         ctx.sv = None
         needs = ctx.needs_input_grad[8:]
         grads = [g if need else None for g, need in zip(grads, needs)]
-        return (None,) * 8 + tuple(grads)
+        return (None, None, None, dfeats, dlocs, None, None, None) + tuple(grads)
 
 
 UC2TrunkFunction = TrunkFunction

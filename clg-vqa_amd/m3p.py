@@ -21,7 +21,8 @@ from . import ops
 from .config import M3PConfig
 from .encoders import GeLU, PreTrainedModel, SimpleClassifier, VLLinear  # noqa: F401
 from .head import TaskHead
-from .engine import BF16, EPI_F32, EngineBase, LayerSpec, LayerStack, TrunkFunction, dw_gemm, linear_params
+from .engine import (BF16, EPI_F32, EngineBase, LayerSpec, LayerStack, TrunkFunction, dw_gemm, input_grad_feats,
+                     input_grad_locs, linear_params)
 
 N_MAX_POSITIONS = 514
 
@@ -216,7 +217,8 @@ class M3PEngine(EngineBase):
                   z2=a32, mean_2=mean_2, rstd_2=rstd_2, z_t=z_t, mean_t=mean_t, rstd_t=rstd_t)
         return self.stack.forward(ar, pw["layers"], p_hid, p_att, seed0, row_post=rowmask), sv
 
-    def backward(self, sv, dx):
+    def backward(self, sv, dx, want_feats=False, want_locs=False):
+        """Returns (grads in ``param_list`` order, d(features) [B,V,F] or None, d(box locations) [B,V,L] or None)."""
         c = self.model.config
         e = self.model.bert.encoder
         ie = e.image_embeddings
@@ -262,10 +264,13 @@ class M3PEngine(EngineBase):
         dWl = torch.zeros_like(ie.image_location_embeddings.weight)
         dbl = torch.zeros_like(ie.image_location_embeddings.bias)
         ops.loc_linear_bwd(sv["locs"], dz1, dWl, dbl, BV, L, H)
+        # (rows beyond a sample's length carry an exactly zero dz1 / dimg16: so do their input gradients)
+        dfeats = input_grad_feats(dimg16, pw["img"].hi).view(B, V, F) if want_feats else None
+        dlocs = input_grad_locs(dz1, ie.image_location_embeddings.weight.detach()).view(B, V, L) if want_locs else None
         grads = [dpos, None if use_sink else dword, dg_t + dg_2, db_t + db_2, dWimg, dbias_img, dWl, dbl, dg_i, db_i]
         for lg in layer_grads:
             grads += lg
-        return grads
+        return grads, dfeats, dlocs
 
 
 class M3PForVLTasks(PreTrainedModel):

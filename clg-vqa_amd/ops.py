@@ -433,6 +433,12 @@ def loc_linear_bwd(loc, dy32, dw, db, R, L, H, deterministic=None):
                "vl_loc_linear_bwd")
 
 
+def loc_linear_bwd_input(dy32, w, dloc32, R, L, H):
+    """dloc32 [R, L] = dy32 [R, H] . w [H, L]: the gradient with respect to the box coordinates (fp32, fixed order)."""
+    _lib.check(_lib.lib().vl_loc_linear_bwd_input(_p(dy32), _p(w), _p(dloc32), R, L, H, _stream()),
+               "vl_loc_linear_bwd_input")
+
+
 def scatter_add_det(tables, dz32, R, H):
     """Deterministic scatter-add of the rows of dz32 [R, H] into several tables at once (csrc/scatter.hip).
     tables = [(ids int64 [R], kind, table fp32 [rows, H], skip, row_flags or None, T)] -- see vl_scatter_add_det."""

@@ -482,6 +482,11 @@ int vl_loc_linear_fwd(const float* loc, const float* w, const float* b, float* y
 int64_t vl_loc_bwd_ws_floats(int64_t R, int64_t H);
 int vl_loc_linear_bwd(const float* loc, const float* dy32, float* dw, float* db, int64_t R, int64_t L, int64_t H,
                       float* ws, void* stream);
+/* Gradient of the projection with respect to the box coordinates themselves (input saliency / attribution; the reference's
+ * autograd through embeddings.py:661-664 and through m3p_transformer.py's BertImageEmbeddings):
+ * dloc32[r,l] = sum_h dy32[r,h] * w[h,l];  w [H,L] as nn.Linear(L,H).weight;  L <= 8, H % 4 == 0, H <= 2048; dy32 16-byte
+ * aligned.  fp32 throughout, fixed summation order (no atomics): two calls give the same bits.  dloc32 is overwritten. */
+int vl_loc_linear_bwd_input(const float* dy32, const float* w, float* dloc32, int64_t R, int64_t L, int64_t H, void* stream);
 /* DETERMINISTIC scatter-add of gradient rows into up to 4 embedding tables that all take their rows from dz32 [R, H]
  * (csrc/scatter.hip): the backward of nn.Embedding(sparse=False) (word / position / token-type tables of UC2Embeddings,
  * volta/volta/embeddings.py:617-655; M3P's self.embeddings(x), m3p_transformer.py:908) with a FIXED summation order -- sort
