@@ -19,7 +19,8 @@ from torch import nn
 
 from . import ops
 from .config import BertConfig, uc2_topology_check
-from .engine import UC2Engine, UC2TrunkFunction, PreparedWeight, dw_gemm, linear_params, _ceil8
+from .engine import UC2Engine, TrunkFunction, PreparedWeight, dw_gemm, linear_params
+from .head import TaskHead
 from .ops import BF16, EPI_F32
 
 logger = logging.getLogger(__name__)
@@ -318,16 +319,15 @@ class PreTrainedModel(nn.Module):
         return model
 
 
-class BertForVLTasks(PreTrainedModel):
-    """Drop-in for volta.encoders.BertForVLTasks (encoders.py:1154-1259) on the VL-classifier(-GQA) path."""
-
-    config_class = BertConfig
+class VLTasksModel(PreTrainedModel):
+    """What the *ForVLTasks models share: trunk (`bert_class`) -> pooler -> dropout -> one SimpleClassifier per task, bound
+    to the native engine (`engine_class`).  A subclass names the two classes and the pooler's activation (`pooler_act`)
+    and keeps its own forward."""
 
     def __init__(self, config, task_cfg, task_ids, dropout_prob=0.1):
         super().__init__(config)
-        self.bert = BertModel(config)
+        self.bert = self.bert_class(config)
         self.dropout = nn.Dropout(dropout_prob)
-        self.config = config
         self.task_cfg = task_cfg
         task2clf = {}
         for task_id in task_ids:
@@ -340,7 +340,7 @@ class BertForVLTasks(PreTrainedModel):
         self.clfs_dict = nn.ModuleDict(task2clf)
         self.fusion_method = config.fusion_method
         self.apply(self.init_weights)
-        object.__setattr__(self, "_engine", UC2Engine(self))
+        object.__setattr__(self, "_engine", self.engine_class(self))
 
     @property
     def engine(self):
@@ -355,6 +355,24 @@ class BertForVLTasks(PreTrainedModel):
             object.__setattr__(self, "_vl_linears", lins)
         for m in lins:
             object.__setattr__(m, "_vl_dirty", True)
+
+    def _task_head(self, task_id):
+        heads = self.__dict__.setdefault("_vl_heads", {})
+        if task_id not in heads:
+            heads[task_id] = TaskHead(self._engine, self._engine.pooler_linear(), self.pooler_act, self.dropout,
+                                      self.clfs_dict[task_id])
+        return heads[task_id]
+
+
+class BertForVLTasks(VLTasksModel):
+    """Drop-in for volta.encoders.BertForVLTasks (encoders.py:1154-1259) on the VL-classifier(-GQA) path."""
+
+    config_class = BertConfig
+    bert_class, engine_class = BertModel, UC2Engine
+
+    @property
+    def pooler_act(self):
+        return self.config.fusion_act
 
     def forward(self, input_txt, input_imgs, image_loc, task_id, token_type_ids=None, attention_mask=None,
                 image_attention_mask=None, output_all_encoded_layers=False, output_all_attention_masks=False):
@@ -373,8 +391,8 @@ class BertForVLTasks(PreTrainedModel):
         self._engine.grad_mode = torch.is_grad_enabled()
         self._engine.tap_request = taps
         try:
-            x = UC2TrunkFunction.apply(self._engine, self.training, input_txt, input_imgs, image_loc, token_type_ids,
-                                       attention_mask, image_attention_mask, *params)
+            x = TrunkFunction.apply(self._engine, self.training, input_txt, input_imgs, image_loc, token_type_ids,
+                                    attention_mask, image_attention_mask, *params)
         finally:
             self._engine.tap_request = None  # (a call that failed before the engine took the request must not leave it behind)
         if self._engine.chunks_pending:  # a pipelined optimizer update: the heads' parameters are its last chunk
@@ -421,11 +439,3 @@ class BertForVLTasks(PreTrainedModel):
         if taps is not None:
             taps.pop("qkv")  # (the training arena's own buffers, or this call's per-layer copies: not part of the result)
         return list_t, list_v
-
-    def _task_head(self, task_id):
-        heads = self.__dict__.setdefault("_vl_heads", {})
-        if task_id not in heads:
-            from .head import TaskHead
-            heads[task_id] = TaskHead(self._engine, self.bert.t_pooler.dense, self.config.fusion_act, self.dropout,
-                                      self.clfs_dict[task_id])
-        return heads[task_id]

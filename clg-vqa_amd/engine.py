@@ -24,7 +24,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import header_constants
-from .ops import BF16, EPI_BF16, EPI_DGELU_BF16, EPI_F32, EPI_GELU_SPLIT
+from .ops import BF16, EPI_F32
 
 VL = header_constants()  # VL_ST_* / VL_LY_* descriptor field indices, parsed from include/vlhip.h
 
@@ -124,6 +124,27 @@ class PreparedWeight(object):
 def _src_ptrs(lin):
     w, m = linear_params(lin)
     return (w.data_ptr(), 0 if m is None else m.data_ptr())
+
+
+def prep_table(pws, device):
+    """The vl_weight_prep_multi table of a list of PreparedWeight (rows + each row's first tile, on the device), its tile
+    count, and the packed [Q|K|V] bias copies as (destination views, source biases): built once per parameter placement
+    -- ~150 tensor slices / detaches per step otherwise, on the host's critical path at the step boundary."""
+    rows, tiles = [], 0
+    for r in (r for p in pws for r in p.descriptors()):
+        rows.append(r + [tiles])
+        tiles += ((r[5] + 63) // 64) * ((r[6] + 63) // 64)
+    pairs = [pr for p in pws for pr in p.bias_pairs()]
+    return dict(table=torch.tensor(rows, dtype=torch.int64).to(device) if rows else None, nrows=len(rows), tiles=tiles,
+                bias_dst=[d for d, _ in pairs], bias_src=[s_ for _, s_ in pairs])
+
+
+def run_prep(tab):
+    """One weight-preparation launch + one multi-tensor bias copy for a prep_table(), on the CURRENT native / torch stream."""
+    if tab["nrows"]:
+        ops.weight_prep_multi(tab["table"], tab["nrows"], tab["tiles"])
+    if tab["bias_dst"]:
+        torch._foreach_copy_(tab["bias_dst"], tab["bias_src"])
 
 
 def dw_gemm(dy16, x16, M, N, K, mask=None):
@@ -228,15 +249,24 @@ class LayerSpec(object):
         return ps
 
 
-def _masked(dw, lin):
-    m = linear_params(lin)[1]
-    if m is not None:  # SFT: grad(weight_orig) = grad(weight) (*) mask  (train_task_sft.py:128-132 autograd)
-        ops.mask_mul(dw, m, dw)
-    return dw
-
-
 def _f32_bits(x):
     return int(np.float32(x).view(np.uint32))
+
+
+def _layer_off(l):
+    """Index of layer l's record in the stack descriptor."""
+    return VL["VL_ST_FIELDS"] + l * VL["VL_LY_FIELDS"]
+
+
+def _layer_fields(sp, lw):
+    """(VL_LY_ field, tensor) of the pointers of one layer that can move between calls: its prepared weights
+    (LayerStack.make_prepared) and its LayerNorm parameters."""
+    qkv, o, w1, w2 = lw["qkv"], lw["o"], lw["w1"], lw["w2"]
+    return (("WQKV_HI", qkv.hi), ("WQKV_LO", qkv.lo), ("WQKV_T", qkv.t_hi), ("BQKV", qkv.bias),
+            ("WO_HI", o.hi), ("WO_LO", o.lo), ("WO_T", o.t_hi), ("BO", o.bias),
+            ("W1_HI", w1.hi), ("W1_LO", w1.lo), ("W1_T", w1.t_hi), ("B1", w1.bias),
+            ("W2_HI", w2.hi), ("W2_LO", w2.lo), ("W2_T", w2.t_hi), ("B2", w2.bias),
+            ("LN1_G", sp.ln1.weight), ("LN1_B", sp.ln1.bias), ("LN2_G", sp.ln2.weight), ("LN2_B", sp.ln2.bias))
 
 
 class ArenaTicket(object):
@@ -286,7 +316,7 @@ class StackArena(object):
         self.qkv_hi, self.qkv_lo = b16(n, M, 3 * H), b16(n, M, 3 * H)
         self.ctx_hi, self.ctx_lo, self.lse = b16(n, M, H), b16(n, M, H), f32(n, B * nh * S)
         self.z1, self.mean1, self.rstd1 = f32(n, M, H), f32(n, M), f32(n, M)
-        self.x1_32, self.x1_hi, self.x1_lo = f32(M, H), b16(n, M, H), b16(M, H)
+        self.x1_hi, self.x1_lo = b16(n, M, H), b16(M, H)
         self.u16, self.h_hi, self.h_lo = b16(n, M, I), b16(n, M, I), b16(M, I)
         self.z2, self.mean2, self.rstd2 = f32(n, M, H), f32(n, M), f32(n, M)
         self.addmask, self.row_post = f32(M), f32(M)
@@ -382,17 +412,14 @@ class LayerStack(object):
         self._desc = {}
         self.prof = None  # numpy int64 VlProf block (bench.py): GEMM launch timing by caller-owned events
 
-    def _new_side_stream(self, dev):
-        # optimizer-only work must not starve the critical path of CUs: the side stream gets the LOWEST queue priority
-        # (side_priority: None = lowest the runtime offers; an int = that priority)
-        pr = self.side_priority
-        if pr is None:
-            pr = max(torch.cuda.Stream.priority_range())
-        return torch.cuda.Stream(device=dev, priority=pr)
-
     def side_stream(self, dev):
         if self._side is None or self._side.device != dev:
-            self._side = self._new_side_stream(dev)
+            # optimizer-only work must not starve the critical path of CUs: the side stream gets the LOWEST queue priority
+            # (side_priority: None = lowest the runtime offers; an int = that priority)
+            pr = self.side_priority
+            if pr is None:
+                pr = max(torch.cuda.Stream.priority_range())
+            self._side = torch.cuda.Stream(device=dev, priority=pr)
         return self._side
 
     def make_prepared(self, device):
@@ -421,10 +448,7 @@ class LayerStack(object):
         """numpy int64 descriptor of (arena, prepared weights, parameters, masks): rebuilt only when a pointer moved."""
         ptrs = []
         for sp, lw in zip(self.specs, pw_layers):
-            for k in ("qkv", "o", "w1", "w2"):
-                p = lw[k]
-                ptrs += [p.hi.data_ptr(), p.lo.data_ptr(), p.t_hi.data_ptr(), p.bias.data_ptr()]
-            ptrs += [sp.ln1.weight.data_ptr(), sp.ln1.bias.data_ptr(), sp.ln2.weight.data_ptr(), sp.ln2.bias.data_ptr()]
+            ptrs += [t.data_ptr() for _, t in _layer_fields(sp, lw)]
             for lin in (sp.q, sp.k, sp.v, sp.o, sp.w1, sp.w2):
                 m = linear_params(lin)[1]
                 ptrs.append(0 if m is None else m.data_ptr())
@@ -433,8 +457,7 @@ class LayerStack(object):
         if hit is not None and hit[0] == fp:
             return hit[1]
         L = len(self.specs)
-        F, LF = VL["VL_ST_FIELDS"], VL["VL_LY_FIELDS"]
-        d = np.zeros(F + L * LF, dtype=np.int64)
+        d = np.zeros(_layer_off(L), dtype=np.int64)
         d[VL["VL_ST_MAGIC"]] = VL["VL_ST_MAGIC_VALUE"]
         for k, v in (("B", ar.B), ("S", ar.S), ("H", self.H), ("I", self.I), ("NH", self.nh), ("NLAYERS", L)):
             d[VL["VL_ST_" + k]] = v
@@ -449,8 +472,8 @@ class LayerStack(object):
                 if ar.images or k.startswith("cs_"):
                     d[VL["VL_ST_" + k.upper()]] = getattr(ar, k).data_ptr()
         it = iter(ptrs)
-        for l in range(L):
-            y = F + l * LF
+        for l, (sp, lw) in enumerate(zip(self.specs, pw_layers)):
+            y = _layer_off(l)
 
             def put(name, t):
                 d[y + VL["VL_LY_" + name]] = t if isinstance(t, int) else t.data_ptr()
@@ -458,18 +481,14 @@ class LayerStack(object):
             put("X_HI", ar.x_hi[l] if ar.need_grad else ar.x_hi[l % 2])  # per layer when backward needs it, else ping-pong
             put("OUT32", ar.x32[(l + 1) % 2]); put("OUT_LO", ar.x_lo[(l + 1) % 2])
             put("OUT_HI", ar.x_hi[l + 1] if ar.need_grad else ar.x_hi[(l + 1) % 2])
-            for k in ("QKV", "O", "W1", "W2"):
-                for suffix in ("_HI", "_LO", "_T"):
-                    put("W" + k + suffix if k in ("QKV", "O") else k + suffix, next(it))
-                put("B" + (k if k in ("QKV", "O") else k[1:]), next(it))
-            for name in ("LN1_G", "LN1_B", "LN2_G", "LN2_B"):
-                put(name, next(it))
+            for name, _ in _layer_fields(sp, lw):
+                put(name, next(it))  # (the fingerprinted pointers: what is written is what is compared)
             for i in range(6):
                 d[y + VL["VL_LY_MASK0"] + i] = next(it)
             for name in ("qkv_hi", "qkv_lo", "ctx_hi", "ctx_lo", "lse", "z1", "mean1", "rstd1", "x1_hi", "u16", "h_hi", "z2",
                          "mean2", "rstd2"):
                 put(name.upper(), ar.lay(getattr(ar, name), l))
-            put("X1_32", ar.x1_32); put("X1_LO", ar.x1_lo); put("H_LO", ar.h_lo)
+            put("X1_LO", ar.x1_lo); put("H_LO", ar.h_lo)
             if ar.need_grad:
                 put("DX", ar.dbuf[l % 2])
                 put("DY", ar.dbuf[(l + 1) % 2])  # (the top layer's DY is patched per backward)
@@ -499,7 +518,6 @@ class LayerStack(object):
         d = d.copy()
         L, B, S, H, nh = len(self.specs), ar.B, ar.S, self.H, self.nh
         dev = ar.x32.device
-        F, LF = VL["VL_ST_FIELDS"], VL["VL_LY_FIELDS"]
         f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
         if taps.get("hidden"):
             taps["x1"], taps["out"] = [f32(B, S, H) for _ in range(L)], [f32(B, S, H) for _ in range(L)]
@@ -511,7 +529,7 @@ class LayerStack(object):
                 taps["qkv"] = [(torch.empty(B * S, 3 * H, dtype=BF16, device=dev), torch.empty(B * S, 3 * H, dtype=BF16, device=dev))
                                for _ in range(L)]
         for l in range(L):
-            y = F + l * LF
+            y = _layer_off(l)
             if taps.get("hidden"):
                 d[y + VL["VL_LY_TAP_X1"]], d[y + VL["VL_LY_TAP_OUT"]] = taps["x1"][l].data_ptr(), taps["out"][l].data_ptr()
             if taps.get("probs"):
@@ -519,18 +537,17 @@ class LayerStack(object):
                 d[y + VL["VL_LY_QKV_HI"]], d[y + VL["VL_LY_QKV_LO"]] = (t.data_ptr() for t in taps["qkv"][l])
         return d
 
-    def forward(self, ar, pw_layers, p_hid, p_att, seed0, row_post=None, taps=None):
-        """`taps`: None, or a dict {"hidden": bool, "probs": bool} that asks for the per-layer outputs of this call and
-        receives them (_tap); such a call runs the last layer dense."""
-        pooled = self.pooled_only and taps is None
-        d = self._descriptor(ar, pw_layers)
-        if taps is not None:
-            d = self._tap(d, ar, taps)
+    def _set_call_fields(self, d, ar, p_hid, p_att, seed0, row_post, pooled, knobs=True):
+        """The descriptor fields that change from call to call.  A backward runs on its forward's descriptor and renews
+        the dropout, row-mask, timing and pooled-row fields only (`knobs` False): the A/B knobs, the per-layer events and
+        the stream-K workspace stay as that forward set them."""
         d[VL["VL_ST_P_HID"]], d[VL["VL_ST_P_ATT"]] = _f32_bits(p_hid), _f32_bits(p_att)
         d[VL["VL_ST_SEED0"]] = seed0
         d[VL["VL_ST_ROW_POST"]] = 0 if row_post is None else ar.row_post.data_ptr()
         d[VL["VL_ST_PROF"]] = 0 if self.prof is None else self.prof.ctypes.data
         d[VL["VL_ST_POOLED_ONLY"]] = 1 if pooled else 0
+        if not knobs:
+            return
         d[VL["VL_ST_TR_BLOCKS_FWD"]], d[VL["VL_ST_TR_BLOCKS_BWD"]] = self.tr_blocks
         d[VL["VL_ST_TR_BWD_LAYERS"]] = len(self.specs) - 1 if self.tr_bwd_layers is None else self.tr_bwd_layers
         d[VL["VL_ST_FUSE_IMAGES"]] = self.fuse_images
@@ -538,9 +555,8 @@ class LayerStack(object):
         d[VL["VL_ST_DX_TILE"]] = int(self.dx_tile)
         d[VL["VL_ST_GEMM_PERSIST"]] = int(self.gemm_persist[0]) | (int(self.gemm_persist[1]) << 16)
         evs = self.layer_ready_events  # set by the engine when an optimizer update is running under this forward
-        F_, LF_ = VL["VL_ST_FIELDS"], VL["VL_LY_FIELDS"]
         for l in range(len(self.specs)):
-            d[F_ + l * LF_ + VL["VL_LY_EV_READY"]] = 0 if evs is None else evs[l].cuda_event
+            d[_layer_off(l) + VL["VL_LY_EV_READY"]] = 0 if evs is None else evs[l].cuda_event
         sk = max(int(self.dw_budget), int(self.dw_tail_budget))
         if ar.need_grad and sk > 0:
             if ar.dw_sk_ws is None or ar.dw_sk_budget != sk:
@@ -551,37 +567,38 @@ class LayerStack(object):
             d[VL["VL_ST_DW_SK_WS_BYTES"]] = ar.dw_sk_ws.numel()
         else:
             d[VL["VL_ST_DW_BUDGET"]] = d[VL["VL_ST_DW_TAIL_BUDGET"]] = 0
+
+    def forward(self, ar, pw_layers, p_hid, p_att, seed0, row_post=None, taps=None):
+        """`taps`: None, or a dict {"hidden": bool, "probs": bool} that asks for the per-layer outputs of this call and
+        receives them (_tap); such a call runs the last layer dense."""
+        pooled = self.pooled_only and taps is None
+        d = self._descriptor(ar, pw_layers)
+        if taps is not None:
+            d = self._tap(d, ar, taps)
+        self._set_call_fields(d, ar, p_hid, p_att, seed0, row_post, pooled)
         side_ptr = None
         if ar.need_grad and self.overlap_dw:
-            dev = ar.x32.device
-            if self._side is None or self._side.device != dev:
-                self._side = self._new_side_stream(dev)
+            side = self.side_stream(ar.x32.device)
             # (a forward whose backward never ran may still have its re-layout in flight on the side stream)
-            torch.cuda.current_stream().wait_stream(self._side)
-            side_ptr = self._side.cuda_stream
-        ops.stack_fwd(d, 0, len(self.specs), side_ptr)
-        ar.desc = d  # backward re-uses it (same pointers: nothing can move between a forward and its backward)
+            torch.cuda.current_stream().wait_stream(side)
+            side_ptr = side.cuda_stream
         L = len(self.specs)
+        ops.stack_fwd(d, 0, L, side_ptr)
+        ar.desc = d  # backward re-uses it (same pointers: nothing can move between a forward and its backward)
         if ar.need_grad:
             ar.in_flight = True
         ar.pooled = pooled
         out = ar.x32[L % 2]
-        H = self.H
-        return out[:ar.B].view(ar.B, 1, H) if pooled else out.view(ar.B, ar.S, H)
+        return out[:ar.B].view(ar.B, 1, self.H) if pooled else out.view(ar.B, ar.S, self.H)
 
     def backward(self, ar, pw_layers, dy, p_hid, p_att, seed0, row_post=None):
         """dy [M,H] fp32 = dL/d(stack output).  Returns (dL/d(stack input), per-layer grads in LayerSpec.params order:
         None where the gradient went straight into the optimizer's arena)."""
         L, dev = len(self.specs), dy.device
         d = ar.desc
-        d[VL["VL_ST_P_HID"]], d[VL["VL_ST_P_ATT"]] = _f32_bits(p_hid), _f32_bits(p_att)
-        d[VL["VL_ST_SEED0"]] = seed0
-        d[VL["VL_ST_ROW_POST"]] = 0 if row_post is None else ar.row_post.data_ptr()
-        d[VL["VL_ST_PROF"]] = 0 if self.prof is None else self.prof.ctypes.data
-        d[VL["VL_ST_POOLED_ONLY"]] = 1 if ar.pooled else 0
+        self._set_call_fields(d, ar, p_hid, p_att, seed0, row_post, ar.pooled, knobs=False)
         assert dy.numel() == (ar.B if ar.pooled else ar.B * ar.S) * self.H
-        F, LF = VL["VL_ST_FIELDS"], VL["VL_LY_FIELDS"]
-        d[F + (L - 1) * LF + VL["VL_LY_DY"]] = dy.data_ptr()
+        d[_layer_off(L - 1) + VL["VL_LY_DY"]] = dy.data_ptr()
         layer_grads, accumulate = [], None
         use_sink = self.grad_sink is not None and self.layer_done_hook is not None
         for l, sp in enumerate(self.specs):
@@ -602,16 +619,12 @@ class LayerStack(object):
                 accumulate = acc
             elif accumulate != acc:
                 raise RuntimeError("clg_vqa_amd: layers disagree on gradient accumulation")
-            g0 = F + l * LF + VL["VL_LY_GRAD0"]
+            g0 = _layer_off(l) + VL["VL_LY_GRAD0"]
             for i, v in enumerate(views):
                 d[g0 + i] = v.data_ptr()
         d[VL["VL_ST_ACCUMULATE"]] = 1 if accumulate else 0
         main = torch.cuda.current_stream()
-        side = None
-        if self.overlap_dw:
-            if self._side is None or self._side.device != dev:
-                self._side = self._new_side_stream(dev)
-            side = self._side
+        side = self.side_stream(dev) if self.overlap_dw else None
         side_ptr = side.cuda_stream if side is not None else None
         if self.layer_done_hook is None or not use_sink:
             ops.stack_bwd(d, L, 0, main.cuda_stream, side_ptr)
@@ -689,11 +702,7 @@ class EngineBase(object):
 
     def prepare_chunk(self, c):
         """Weight preparation + packed-bias copies of chunk c on the CURRENT native / torch stream."""
-        ch = self._prepared["chunks"][c]
-        if ch["nrows"]:
-            ops.weight_prep_multi(ch["table"], ch["nrows"], ch["tiles"])
-        if ch["bias_dst"]:
-            torch._foreach_copy_(ch["bias_dst"], ch["bias_src"])
+        run_prep(self._prepared["chunks"][c])
 
     def finish_prepare(self):
         """All chunks were prepared by the optimizer: the next forward only waits for their events."""
@@ -728,8 +737,21 @@ class EngineBase(object):
         return (self._seed0 * 4096 + site) & 0xFFFFFFFFFFFFFFFF
 
     def head_linears(self):
-        """Leaf Linears of the task heads: prepared by the same launch as the trunk's weights."""
-        return []
+        """Leaf Linears of the task heads (the engine's pooler_linear() + every classifier's two): prepared by the same
+        launch as the trunk's weights."""
+        lins = [self.pooler_linear()]
+        for clf in self.model.clfs_dict.values():
+            lins += [clf.logit_fc[0], clf.logit_fc[3]]
+        return lins
+
+    def word_grad_dest(self, table, dev):
+        """(dword, use_sink, defer) of a backward: the word-embedding gradient goes into the optimizer's sink when it
+        matches `table`, else into a fresh zero tensor (use_sink False); with `defer` the rows go to the reducer
+        (_push_word_grad) and there is no destination."""
+        sink = self.word_grad_sink
+        use_sink = sink is not None and sink.shape == table.shape and sink.device == dev
+        defer = use_sink and self.defer_word_grad
+        return None if defer else (sink if use_sink else torch.zeros_like(table)), use_sink, defer
 
     def pooled_split(self, x):
         """(hi, lo) bf16 operand form of the pooled rows when `x` is the output of this engine's last forward in the
@@ -766,32 +788,11 @@ class EngineBase(object):
             # the device table only depends on where the source weights / masks live: compare those pointers first
             ident = tuple(q for p in all_pw for l in p.linears for q in _src_ptrs(l) + (l.bias.data_ptr(),))
             if pw.get("table_ident") != ident:
-                rows, tile0 = [], 0
-                for r in (r for p in all_pw for r in p.descriptors()):
-                    rows.append(r + [tile0])
-                    tile0 += ((r[5] + 63) // 64) * ((r[6] + 63) // 64)
-                pw["table"] = torch.tensor(rows, dtype=torch.int64).to(device)
-                pw["table_ident"], pw["table_tiles"] = ident, tile0
-                # the packed [Q|K|V] bias copies of all layers: (destination views, source biases) built once per
-                # parameter placement -- ~150 tensor slices / detaches per step otherwise, on the host's critical path
-                # at the step boundary
-                pairs = [pr for p in all_pw for pr in p.bias_pairs()]
-                pw["bias_dst"], pw["bias_src"] = [d for d, _ in pairs], [s_ for _, s_ in pairs]
+                pw["table_ident"], pw["table"] = ident, prep_table(all_pw, device)
                 # the same table cut into chunks (embeddings | layer l | heads) for the optimizer's pipelined update
                 groups = [[pw["img"]]] + [[lw[k] for k in ("qkv", "o", "w1", "w2")] for lw in pw["layers"]] + [pw["head"]]
-                chunks = []
-                for grp in groups:
-                    rws, t0 = [], 0
-                    for r in (r for p in grp for r in p.descriptors()):
-                        rws.append(r + [t0])
-                        t0 += ((r[5] + 63) // 64) * ((r[6] + 63) // 64)
-                    prs = [pr for p in grp for pr in p.bias_pairs()]
-                    chunks.append(dict(table=torch.tensor(rws, dtype=torch.int64).to(device) if rws else None, nrows=len(rws),
-                                       tiles=t0, bias_dst=[d for d, _ in prs], bias_src=[s_ for _, s_ in prs]))
-                pw["chunks"] = chunks
-            ops.weight_prep_multi(pw["table"], pw["table"].shape[0], pw["table_tiles"])  # one launch per step
-            if pw["bias_dst"]:  # one multi-tensor copy
-                torch._foreach_copy_(pw["bias_dst"], pw["bias_src"])
+                pw["chunks"] = [prep_table(grp, device) for grp in groups]
+            run_prep(pw["table"])  # one launch + one multi-tensor copy per step
             for p in all_pw:
                 p.refresh_bias(fingerprint=not explicit, pack=False)
         self._dirty = False
@@ -821,11 +822,8 @@ class UC2Engine(EngineBase):
     def image_linear(self):
         return self.model.bert.embeddings.image_embeddings
 
-    def head_linears(self):
-        lins = [self.model.bert.t_pooler.dense]
-        for clf in self.model.clfs_dict.values():
-            lins += [clf.logit_fc[0], clf.logit_fc[3]]
-        return lins
+    def pooler_linear(self):
+        return self.model.bert.t_pooler.dense
 
     # ---- parameters ------------------------------------------------------------------------------------------
     def param_list(self):
@@ -853,7 +851,7 @@ class UC2Engine(EngineBase):
         V, F = feats.shape[1], feats.shape[2]
         L = locs.shape[2]
         S, H = T + V, self.H
-        M, BT, BV = B * S, B * T, B * V
+        BT, BV = B * T, B * V
         p_hid = float(cfg.hidden_dropout_prob) if training else 0.0
         p_att = float(cfg.attention_probs_dropout_prob) if training else 0.0
         seed0, seed = self.next_seed()
@@ -939,10 +937,7 @@ class UC2Engine(EngineBase):
 
         # --- embeddings backward (dy = dL/dX0 [M,H]) ---
         type_w = emb.new_token_type_embeddings.weight
-        sink = self.word_grad_sink
-        use_sink = sink is not None and sink.shape == emb.word_embeddings.weight.shape and sink.device == dev
-        defer = use_sink and self.defer_word_grad
-        dword = None if defer else (sink if use_sink else torch.zeros_like(emb.word_embeddings.weight))
+        dword, use_sink, defer = self.word_grad_dest(emb.word_embeddings.weight, dev)
         dpos = torch.zeros_like(emb.position_embeddings.weight)
         dtype_ = torch.zeros_like(type_w)
         # box rows
@@ -1016,6 +1011,3 @@ class TrunkFunction(torch.autograd.Function):
         needs = ctx.needs_input_grad[8:]
         grads = [g if need else None for g, need in zip(grads, needs)]
         return (None, None, None, dfeats, dlocs, None, None, None) + tuple(grads)
-
-
-UC2TrunkFunction = TrunkFunction

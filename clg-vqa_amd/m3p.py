@@ -19,8 +19,7 @@ from torch import nn
 
 from . import ops
 from .config import M3PConfig
-from .encoders import GeLU, PreTrainedModel, SimpleClassifier, VLLinear  # noqa: F401
-from .head import TaskHead
+from .encoders import VLLinear, VLTasksModel
 from .engine import (BF16, EPI_F32, EngineBase, LayerSpec, LayerStack, TrunkFunction, dw_gemm, input_grad_feats,
                      input_grad_locs, linear_params)
 
@@ -145,11 +144,8 @@ class M3PEngine(EngineBase):
     def image_linear(self):
         return self.model.bert.encoder.image_embeddings.image_embeddings
 
-    def head_linears(self):
-        lins = [self.model.bert.pooler.dense]
-        for clf in self.model.clfs_dict.values():
-            lins += [clf.logit_fc[0], clf.logit_fc[3]]
-        return lins
+    def pooler_linear(self):
+        return self.model.bert.pooler.dense
 
     def param_list(self):
         e = self.model.bert.encoder
@@ -233,10 +229,7 @@ class M3PEngine(EngineBase):
                                               sv["seed0"], row_post=sv["rowmask"])
         ge = e.layer_norm_emb.weight.detach()
         dpos = torch.zeros_like(e.position_embeddings.weight)
-        sink = self.word_grad_sink
-        use_sink = sink is not None and sink.shape == e.embeddings.weight.shape and sink.device == dev
-        defer = use_sink and self.defer_word_grad
-        dword = None if defer else (sink if use_sink else torch.zeros_like(e.embeddings.weight))
+        dword, use_sink, defer = self.word_grad_dest(e.embeddings.weight, dev)
         # text rows
         dz_t, dg_t, db_t = f32(BT, H), f32(H), f32(H)
         ops.ln_bwd(dy, sv["z_t"], sv["mean_t"], sv["rstd_t"], ge, dz_t, None, None, dg_t, db_t, None, ws, BT, H, group=T,
@@ -273,42 +266,12 @@ class M3PEngine(EngineBase):
         return grads, dfeats, dlocs
 
 
-class M3PForVLTasks(PreTrainedModel):
+class M3PForVLTasks(VLTasksModel):
     """Drop-in for volta.encoders.M3PForVLTasks (encoders.py:1262-1353) on the VL-classifier(-GQA) path."""
 
     config_class = M3PConfig
-
-    def __init__(self, config, task_cfg, task_ids, dropout_prob=0.1):
-        super().__init__(config)
-        self.bert = M3PModel(config)
-        self.dropout = nn.Dropout(dropout_prob)
-        self.config = config
-        self.task_cfg = task_cfg
-        task2clf = {}
-        for task_id in task_ids:
-            task_type = task_cfg[task_id]["type"]
-            if task_type in {"VL-classifier", "VL-classifier-GQA"}:
-                task2clf[task_id] = SimpleClassifier(config.pooler_size, config.clf_hidden_size,
-                                                     task_cfg[task_id]["num_labels"], config.layer_norm_eps)
-            else:
-                raise ValueError("clg_vqa_amd supports VL-classifier / VL-classifier-GQA heads only (got %s)" % task_type)
-        self.clfs_dict = nn.ModuleDict(task2clf)
-        self.fusion_method = config.fusion_method
-        self.apply(self.init_weights)
-        object.__setattr__(self, "_engine", M3PEngine(self))
-
-    @property
-    def engine(self):
-        return self._engine
-
-    def mark_weights_dirty(self):
-        self._engine.mark_dirty()
-        lins = self.__dict__.get("_vl_linears")
-        if lins is None:
-            lins = [m for m in self.modules() if isinstance(m, VLLinear)]
-            object.__setattr__(self, "_vl_linears", lins)
-        for m in lins:
-            object.__setattr__(m, "_vl_dirty", True)
+    bert_class, engine_class = M3PModel, M3PEngine
+    pooler_act = "tanh"
 
     def forward(self, input_txt, input_imgs, image_loc, task_id, token_type_ids=None, attention_mask=None,
                 image_attention_mask=None, output_all_encoded_layers=False, output_all_attention_masks=False):
@@ -323,9 +286,3 @@ class M3PForVLTasks(PreTrainedModel):
             return head(x, self.training), None, None, None
         pooled_output = self.dropout(self.bert.pooler(x))
         return self.clfs_dict[task_id](pooled_output), None, None, None
-
-    def _task_head(self, task_id):
-        heads = self.__dict__.setdefault("_vl_heads", {})
-        if task_id not in heads:
-            heads[task_id] = TaskHead(self._engine, self.bert.pooler.dense, "tanh", self.dropout, self.clfs_dict[task_id])
-        return heads[task_id]

@@ -61,6 +61,15 @@ def _pld(t):
     return t.data_ptr(), t.stride(0)
 
 
+def _table(width, rows):
+    """`rows` (sequences of `width` integers: one problem / entry of a grouped launch each) as the flat int64 table the
+    C ABI takes; pass it as ctypes.cast(table, ctypes.c_void_p)."""
+    arr = (ctypes.c_int64 * (width * len(rows)))()
+    for i, r in enumerate(rows):
+        arr[width * i:width * (i + 1)] = r
+    return arr
+
+
 _SMALL_WS = {}
 SMALL_GEMM = True  # A/B knob (bench.py BENCH_NO_SMALL_GEMM): False = batch-sized products on the big-tile kernels
 
@@ -82,7 +91,6 @@ def gemm_nt(a_hi, a_lo, b_hi, b_lo, M, N, K, passes, epilogue, bias=None, resid=
     with a small M (the batch-sized products of the head) get a workspace and take the library's small-M path.
     image / image_cols: also store out_hi as the K-major image of the weight-gradient GEMM; colsum [rows, N] fp32:
     column-sum partials of out_hi (DGELU epilogue, ping-pong kernel) -- returns the number of partial rows written."""
-    import ctypes
     pa, lda = _pld(a_hi)
     pb, ldb = _pld(b_hi)
     pal = _pld(a_lo)[0] if a_lo is not None else None
@@ -158,18 +166,12 @@ def stack_bwd(desc, layer_hi, layer_lo, stream_main, stream_side):
 
 def transpose_blocked(entries, M, max_blocks=0):
     """entries = [(src [M,N] bf16 (row-major, ld = stride(0)), dst blocked image, colsum_partial or None), ...]"""
-    import ctypes
-    n = len(entries)
-    arr = (ctypes.c_int64 * (6 * n))()
-    for i, (src, dst, cs) in enumerate(entries):
-        ps, ld = _pld(src)
-        arr[6 * i:6 * i + 6] = [ps, ld, src.shape[1], _p(dst), 0 if cs is None else _p(cs), 0]
-    _lib.check(_lib.lib().vl_transpose_blocked(ctypes.cast(arr, ctypes.c_void_p), n, M, max_blocks, _stream()),
+    arr = _table(6, [_pld(src) + (src.shape[1], _p(dst), 0 if cs is None else _p(cs), 0) for src, dst, cs in entries])
+    _lib.check(_lib.lib().vl_transpose_blocked(ctypes.cast(arr, ctypes.c_void_p), len(entries), M, max_blocks, _stream()),
                "vl_transpose_blocked")
 
 
 def colsum_finalize(partial, nblk, N, outs, accumulate=False):
-    import ctypes
     arr = (ctypes.c_void_p * len(outs))(*[_p(o) for o in outs])
     _lib.check(_lib.lib().vl_colsum_finalize(_p(partial), nblk, N, ctypes.cast(arr, ctypes.c_void_p), len(outs),
                                              1 if accumulate else 0, _stream()), "vl_colsum_finalize")
@@ -177,58 +179,44 @@ def colsum_finalize(partial, nblk, N, outs, accumulate=False):
 
 def colreduce_multi(sets, accumulate=False):
     """sets = [(src [nrows, ncols] fp32, seg, (out0, out1, out2) with None = skip), ...] (<= 4): one launch."""
-    import ctypes
-    n = len(sets)
-    arr = (ctypes.c_int64 * (8 * n))()
-    for i, (src, seg, outs) in enumerate(sets):
-        o = [0 if t is None else _p(t) for t in outs] + [0] * (3 - len(outs))
-        arr[8 * i:8 * i + 8] = [_p(src), src.shape[0], src.shape[1], seg] + o + [0]
-    _lib.check(_lib.lib().vl_colreduce_multi(ctypes.cast(arr, ctypes.c_void_p), n, 1 if accumulate else 0, _stream()),
-               "vl_colreduce_multi")
+    arr = _table(8, [[_p(src), src.shape[0], src.shape[1], seg] + [0 if t is None else _p(t) for t in outs]
+                     + [0] * (4 - len(outs)) for src, seg, outs in sets])
+    _lib.check(_lib.lib().vl_colreduce_multi(ctypes.cast(arr, ctypes.c_void_p), len(sets), 1 if accumulate else 0,
+                                             _stream()), "vl_colreduce_multi")
 
 
 def dw_grouped(problems, K, accumulate=False):
     """problems = [(aT_ptr_tensor, a_row0, a_rows_total, bT_tensor, b_rows_total, out [M,N] fp32, mask or None, M, N)]:
     aT / bT are blocked images (transpose_blocked); a_row0 selects a row sub-range of the A image."""
-    import ctypes
-    n = len(problems)
-    arr = (ctypes.c_int64 * (10 * n))()
-    for i, (aT, a_row0, a_rows, bT, b_rows, out, mask, M, N) in enumerate(problems):
+    rows = []
+    for aT, a_row0, a_rows, bT, b_rows, out, mask, M, N in problems:
         assert out.dtype == torch.float32 and out.stride(1) == 1
-        arr[10 * i:10 * i + 10] = [_p(aT) + 2 * 64 * a_row0, a_rows, _p(bT), b_rows, out.data_ptr(), out.stride(0),
-                                   0 if mask is None else _p(mask), M, N, 0]
-    _lib.check(_lib.lib().vl_dw_grouped(ctypes.cast(arr, ctypes.c_void_p), n, K, 1 if accumulate else 0, _stream()),
-               "vl_dw_grouped")
+        rows.append([_p(aT) + 2 * 64 * a_row0, a_rows, _p(bT), b_rows, out.data_ptr(), out.stride(0),
+                     0 if mask is None else _p(mask), M, N, 0])
+    _lib.check(_lib.lib().vl_dw_grouped(ctypes.cast(_table(10, rows), ctypes.c_void_p), len(rows), K, 1 if accumulate else 0,
+                                        _stream()), "vl_dw_grouped")
 
 
 def dw_grouped_rowmajor(problems, rows, accumulate=False):
     """problems = [(dY [rows, >= M] bf16 view (row-major, ld = stride(0)), X [rows, >= N] bf16, out [M,N] fp32, mask or None,
     M, N, colsum partials [ceil(N/256), M] fp32 or None)]: out (+)= dY[:, :M]^T . X[:, :N] from the row-major operands."""
-    import ctypes
-    n = len(problems)
-    arr = (ctypes.c_int64 * (10 * n))()
-    for i, (dy, x, out, mask, M, N, cs) in enumerate(problems):
-        pa, lda = _pld(dy)
-        pb, ldb = _pld(x)
+    tab = []
+    for dy, x, out, mask, M, N, cs in problems:
         assert out.dtype == torch.float32 and out.stride(1) == 1
-        arr[10 * i:10 * i + 10] = [pa, lda, pb, ldb, out.data_ptr(), out.stride(0), 0 if mask is None else _p(mask), M, N,
-                                   0 if cs is None else _p(cs)]
-    _lib.check(_lib.lib().vl_dw_grouped_rowmajor(ctypes.cast(arr, ctypes.c_void_p), n, rows, 1 if accumulate else 0,
-                                                 _stream()), "vl_dw_grouped_rowmajor")
+        tab.append(_pld(dy) + _pld(x) + (out.data_ptr(), out.stride(0), 0 if mask is None else _p(mask), M, N,
+                                         0 if cs is None else _p(cs)))
+    _lib.check(_lib.lib().vl_dw_grouped_rowmajor(ctypes.cast(_table(10, tab), ctypes.c_void_p), len(tab), rows,
+                                                 1 if accumulate else 0, _stream()), "vl_dw_grouped_rowmajor")
 
 
 def dw_grouped_mixed(problems, rows, mode, accumulate=False, budget=0, ws=None):
     """problems = [(a, a_cols, b, b_cols, out, mask, M, N, colsum)]: an operand is a row-major 2-D bf16 view (its *_cols is
     None) when its mode bit is set (bit 0: dY, bit 1: X), else its K-major image (1-D tensor) with the image's column count.
     budget > 0: the stream-K form on that many workgroups with the zero-initialised workspace `ws` (dw_streamk_ws)."""
-    import ctypes
     n = len(problems)
-    arr = (ctypes.c_int64 * (10 * n))()
-    for i, (a, a_cols, b, b_cols, out, mask, M, N, cs) in enumerate(problems):
-        pa, lda = _pld(a) if mode & 1 else (_p(a), a_cols)
-        pb, ldb = _pld(b) if mode & 2 else (_p(b), b_cols)
-        arr[10 * i:10 * i + 10] = [pa, lda, pb, ldb, out.data_ptr(), out.stride(0), 0 if mask is None else _p(mask), M, N,
-                                   0 if cs is None else _p(cs)]
+    arr = _table(10, [(_pld(a) if mode & 1 else (_p(a), a_cols)) + (_pld(b) if mode & 2 else (_p(b), b_cols))
+                      + (out.data_ptr(), out.stride(0), 0 if mask is None else _p(mask), M, N, 0 if cs is None else _p(cs))
+                      for a, a_cols, b, b_cols, out, mask, M, N, cs in problems])
     if budget:
         _lib.check(_lib.lib().vl_dw_grouped_streamk(ctypes.cast(arr, ctypes.c_void_p), n, rows, 1 if accumulate else 0, mode,
                                                     int(budget), _p(ws), ws.numel() * ws.element_size(), _stream()),
@@ -442,12 +430,12 @@ def loc_linear_bwd_input(dy32, w, dloc32, R, L, H):
 def scatter_add_det(tables, dz32, R, H):
     """Deterministic scatter-add of the rows of dz32 [R, H] into several tables at once (csrc/scatter.hip).
     tables = [(ids int64 [R], kind, table fp32 [rows, H], skip, row_flags or None, T)] -- see vl_scatter_add_det."""
-    import ctypes
     n = len(tables)
-    arr = (ctypes.c_int64 * (6 * n))()
-    for i, (ids, kind, table, skip, flags, T) in enumerate(tables):
+    rows = []
+    for ids, kind, table, skip, flags, T in tables:
         assert ids.is_contiguous() and ids.dtype == torch.int64 and table.is_contiguous() and table.dtype == torch.float32
-        arr[6 * i:6 * i + 6] = [_p(ids), kind, _p(table), skip, 0 if flags is None else _p(flags), T]
+        rows.append([_p(ids), kind, _p(table), skip, 0 if flags is None else _p(flags), T])
+    arr = _table(6, rows)
     L = _lib.lib()
     nbytes = L.vl_scatter_det_ws_bytes(n, R, H)
     ws = _ws("scatter", dz32.device, nbytes)
