@@ -56,6 +56,8 @@ _SIGS = {
     "vl_ln_bwd_ws_floats": (c_int64, [c_int64, c_int64]),
     "vl_ln_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int64,
                           c_float, c_float, c_uint64, c_int64, P]),
+    "vl_ln_bwd_add": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int64,
+                              c_float, c_float, c_uint64, c_int64, P]),
     "vl_memset_zero": (c_int, [P, c_int64, P]),
     "vl_gqa_loss_ws_bytes": (c_int64, [c_int64]),
     "vl_gqa_loss": (c_int, [P, P, P, c_int64, c_int64, c_float, P, P, P, P]),

@@ -34,8 +34,8 @@ struct LnArgs {
   // rrstd[row]) + rbeta[c] (* rrow_post[row]), the very expression that LayerNorm stored; it then need not store its fp32
   // output at all (44 MB per launch at c2)
   const float* rz; const float* rmean; const float* rrstd; const float* rgamma; const float* rbeta; const float* rrow_post;
-  // backward
-  const float* dy; const float* z; float* dz; bf16_raw* dpre16; float* dpre32; float* ws; int nblk;
+  // backward (dy_add: optional second fp32 addend of dy, read through the same row map -- ln_bwd_kernel<NV, true>)
+  const float* dy; const float* dy_add; const float* z; float* dz; bf16_raw* dpre16; float* dpre32; float* ws; int nblk;
 };
 
 __device__ __forceinline__ long map_row(const LnArgs& p, long r) {
@@ -147,7 +147,10 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(LnArgs p) {
 #ifndef VL_LN_BWD_RPT
 #define VL_LN_BWD_RPT 4    // rows per trip and wave (loads of all of them are issued before the first is reduced)
 #endif
-template <int NV>
+// ADD: dy is the sum of two fp32 tensors (p.dy + p.dy_add, formed once on load and used wherever dy is): the gradient that
+// arrives at a tapped LayerNorm output from outside the stack joins the one that flows down the stack without a pass of its
+// own over [M, H].
+template <int NV, bool ADD>
 __global__ __launch_bounds__(256, VL_LN_BWD_MINWG) void ln_bwd_kernel(LnArgs p) {
   __shared__ float red[3][4][NV * 256];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -181,6 +184,10 @@ __global__ __launch_bounds__(256, VL_LN_BWD_MINWG) void ln_bwd_kernel(LnArgs p) 
         const int c = (i * 64 + lane) * 4;
         if (c >= p.H) { dy[k][i] = zz[k][i] = make_float4(0.f, 0.f, 0.f, 0.f); continue; }
         dy[k][i] = *reinterpret_cast<const float4*>(p.dy + orow[k] * p.H + c);
+        if (ADD) {
+          const float4 q = *reinterpret_cast<const float4*>(p.dy_add + orow[k] * p.H + c);
+          dy[k][i].x += q.x; dy[k][i].y += q.y; dy[k][i].z += q.z; dy[k][i].w += q.w;
+        }
         zz[k][i] = *reinterpret_cast<const float4*>(p.z + rr[k] * p.H + c);
       }
       // (the row statistics ride with the row loads: fetched inside the per-row section below, each would expose a full
@@ -319,7 +326,10 @@ int launch_fwd(const LnArgs& a, hipStream_t s) {
 }
 template <int NV>
 int launch_bwd(const LnArgs& a, hipStream_t s, float* dgamma, float* dbeta, float* dbias) {
-  hipLaunchKernelGGL((ln_bwd_kernel<NV>), dim3(a.nblk), dim3(256), 0, s, a);
+  if (a.dy_add)
+    hipLaunchKernelGGL((ln_bwd_kernel<NV, true>), dim3(a.nblk), dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL((ln_bwd_kernel<NV, false>), dim3(a.nblk), dim3(256), 0, s, a);
   VL_CHECK_LAUNCH("vl_ln_bwd");
   if (!dgamma && !dbeta && !dbias) return 0;  // partials only: the caller sums them with vl_ln_bwd_reduce
   LnReduceArgs ra{};
@@ -391,11 +401,22 @@ extern "C" int vl_ln_bwd(const float* dy32, const float* z32, const float* mean,
                          const float* gamma, const float* row_pre, const float* row_post, float* dz32, void* dpre16, float* dpre32, float* dgamma, float* dbeta,
                          float* dbias, float* partial_ws, int64_t M, int64_t H, int64_t group, int64_t out_stride,
                          int64_t out_off, float p_pre, float p_post, uint64_t seed, int64_t orig_row_stride, void* stream) {
+  return vl_ln_bwd_add(dy32, nullptr, z32, mean, rstd, gamma, row_pre, row_post, dz32, dpre16, dpre32, dgamma, dbeta, dbias, partial_ws,
+                       M, H, group, out_stride, out_off, p_pre, p_post, seed, orig_row_stride, stream);
+}
+
+// vl_ln_bwd of dy32 + dy_add (fp32 sum formed on load; dy_add = NULL is vl_ln_bwd: the same kernel instantiation)
+extern "C" int vl_ln_bwd_add(const float* dy32, const float* dy_add, const float* z32, const float* mean, const float* rstd,
+                             const float* gamma, const float* row_pre, const float* row_post, float* dz32, void* dpre16, float* dpre32,
+                             float* dgamma, float* dbeta, float* dbias, float* partial_ws, int64_t M, int64_t H, int64_t group,
+                             int64_t out_stride, int64_t out_off, float p_pre, float p_post, uint64_t seed, int64_t orig_row_stride,
+                             void* stream) {
   if (int rc = check_shape("vl_ln_bwd", M, H, group, p_pre, p_post)) return rc;
   VL_CHECK_ARG(orig_row_stride >= 1, "vl_ln_bwd: orig_row_stride must be >= 1");
   VL_CHECK_ARG(dy32 && z32 && mean && rstd && gamma && partial_ws, "vl_ln_bwd: null pointer");
+  VL_CHECK_ARG((reinterpret_cast<uintptr_t>(dy_add) & 15u) == 0, "vl_ln_bwd_add: dy_add must be 16-byte aligned");
   LnArgs a{};
-  a.dy = dy32; a.z = z32; a.mean = const_cast<float*>(mean); a.rstd = const_cast<float*>(rstd); a.gamma = gamma;
+  a.dy = dy32; a.dy_add = dy_add; a.z = z32; a.mean = const_cast<float*>(mean); a.rstd = const_cast<float*>(rstd); a.gamma = gamma;
   a.row_pre = row_pre; a.row_post = row_post;
   a.dz = dz32; a.dpre16 = (bf16_raw*)dpre16; a.dpre32 = dpre32; a.ws = partial_ws; a.nblk = nblk_for(M);
   a.M = M; a.H = (int)H; a.group = group; a.out_stride = out_stride; a.out_off = out_off;

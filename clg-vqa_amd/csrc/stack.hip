@@ -306,11 +306,14 @@ extern "C" int vl_stack_bwd(const int64_t* d, int64_t layer_hi, int64_t layer_lo
     const bool pooled = d[VL_ST_POOLED_ONLY] != 0 && l == L - 1;  // see vl_stack_fwd: DY is the compact [B, H] gradient
     const int64_t R = pooled ? B : M, nq = pooled ? 1 : S, os = pooled ? S : 1;
     VL_CHECK_ARG(!pooled || d[VL_ST_ROWS0], "vl_stack_bwd: the pooled-row mode needs VL_ST_ROWS0");
+    VL_CHECK_ARG(!pooled || (!y[VL_LY_TAP_GRAD_X1] && !y[VL_LY_TAP_GRAD_OUT]),
+                 "vl_stack_bwd: layer %lld runs in the pooled-row mode: it has no taps, so no tap gradient (VL_LY_TAP_GRAD_*)", (long long)l);
     // ---- critical path ------------------------------------------------------------------------------------------
-    VL_TRY(vl_ln_bwd(ptr<const float>(y[VL_LY_DY]), ptr<const float>(y[VL_LY_Z2]), ptr<const float>(y[VL_LY_MEAN2]),
-                     ptr<const float>(y[VL_LY_RSTD2]), ptr<const float>(y[VL_LY_LN2_G]), nullptr, row_post, ptr<float>(y[VL_LY_DZ2]),
-                     ptr<void>(y[VL_LY_DT2]), nullptr, nullptr, nullptr, nullptr, ptr<float>(y[VL_LY_LNWS2]), R, H, R, 0, 0, p_hid, 0.f,
-                     seed_of(d[VL_ST_SEED0], s3 + 2), os, sm));
+    // (a gradient with respect to a tapped hidden state joins the stack's own inside the LayerNorm backward: VL_LY_TAP_GRAD_*)
+    VL_TRY(vl_ln_bwd_add(ptr<const float>(y[VL_LY_DY]), ptr<const float>(y[VL_LY_TAP_GRAD_OUT]), ptr<const float>(y[VL_LY_Z2]),
+                         ptr<const float>(y[VL_LY_MEAN2]), ptr<const float>(y[VL_LY_RSTD2]), ptr<const float>(y[VL_LY_LN2_G]), nullptr,
+                         row_post, ptr<float>(y[VL_LY_DZ2]), ptr<void>(y[VL_LY_DT2]), nullptr, nullptr, nullptr, nullptr,
+                         ptr<float>(y[VL_LY_LNWS2]), R, H, R, 0, 0, p_hid, 0.f, seed_of(d[VL_ST_SEED0], s3 + 2), os, sm));
     const bool fused = fused_du(d, l);
     int64_t cs_du_rows = 0;
     const GemmImage duim{ptr<void>(y[VL_LY_T_DU]), I, ptr<float>(y[VL_LY_CS_DU]), &cs_du_rows};
@@ -319,10 +322,10 @@ extern "C" int vl_stack_bwd(const int64_t* d, int64_t layer_hi, int64_t layer_lo
                 fused ? &duim : nullptr));
     VL_TRY(gemm(gc, ptr<void>(y[VL_LY_DU16]), nullptr, I, ptr<void>(y[VL_LY_W1_T]), nullptr, I, R, H, I, 1, VL_EPI_F32, nullptr,
                 ptr<const float>(y[VL_LY_DZ2]), ptr<float>(y[VL_LY_DX1]), H, nullptr, nullptr, nullptr, 0, sm));
-    VL_TRY(vl_ln_bwd(ptr<const float>(y[VL_LY_DX1]), ptr<const float>(y[VL_LY_Z1]), ptr<const float>(y[VL_LY_MEAN1]),
-                     ptr<const float>(y[VL_LY_RSTD1]), ptr<const float>(y[VL_LY_LN1_G]), nullptr, nullptr, ptr<float>(y[VL_LY_DZ1]),
-                     ptr<void>(y[VL_LY_DT1]), nullptr, nullptr, nullptr, nullptr, ptr<float>(y[VL_LY_LNWS1]), R, H, R, 0, 0, p_hid, 0.f,
-                     seed_of(d[VL_ST_SEED0], s3 + 1), os, sm));
+    VL_TRY(vl_ln_bwd_add(ptr<const float>(y[VL_LY_DX1]), ptr<const float>(y[VL_LY_TAP_GRAD_X1]), ptr<const float>(y[VL_LY_Z1]),
+                         ptr<const float>(y[VL_LY_MEAN1]), ptr<const float>(y[VL_LY_RSTD1]), ptr<const float>(y[VL_LY_LN1_G]), nullptr,
+                         nullptr, ptr<float>(y[VL_LY_DZ1]), ptr<void>(y[VL_LY_DT1]), nullptr, nullptr, nullptr, nullptr,
+                         ptr<float>(y[VL_LY_LNWS1]), R, H, R, 0, 0, p_hid, 0.f, seed_of(d[VL_ST_SEED0], s3 + 1), os, sm));
     VL_TRY(gemm(gc, ptr<void>(y[VL_LY_DT1]), nullptr, H, ptr<void>(y[VL_LY_WO_T]), nullptr, H, R, H, H, 1, VL_EPI_BF16, nullptr,
                 nullptr, nullptr, 0, ptr<void>(y[VL_LY_DCTX16]), nullptr, nullptr, H, sm));
     VL_TRY(vl_attn2_bwd(ptr<void>(y[VL_LY_QKV_HI]), addmask, ptr<void>(y[VL_LY_DCTX16]), ptr<const float>(y[VL_LY_LSE]),

@@ -19,7 +19,7 @@ from torch import nn
 
 from . import ops
 from .config import BertConfig, uc2_topology_check
-from .engine import UC2Engine, TrunkFunction, PreparedWeight, dw_gemm, linear_params
+from .engine import UC2Engine, TrunkFunction, PreparedWeight, differentiable_trunk, dw_gemm, linear_params
 from .head import TaskHead
 from .ops import BF16, EPI_F32
 
@@ -370,6 +370,10 @@ class BertForVLTasks(VLTasksModel):
     config_class = BertConfig
     bert_class, engine_class = BertModel, UC2Engine
 
+    # opt-in: with output_all_encoded_layers=True and grad mode on, encoded_layers_t / encoded_layers_v carry the trunk's
+    # graph, as in the reference (encoders.py:848-892, 1256-1258; engine.differentiable_trunk); default: detached
+    differentiable_encoded_layers = False
+
     @property
     def pooler_act(self):
         return self.config.fusion_act
@@ -382,7 +386,8 @@ class BertForVLTasks(VLTasksModel):
             token_type_ids = torch.zeros_like(input_txt)
         if image_attention_mask is None:
             image_attention_mask = torch.ones(input_imgs.size(0), input_imgs.size(1)).type_as(input_txt)
-        # per-layer outputs (encoders.py:848-892, 1256-1258): taps of the native stack, returned detached.  Attention data
+        # per-layer outputs (encoders.py:848-892, 1256-1258): taps of the native stack, returned detached unless
+        # differentiable_encoded_layers is set (the hidden states then carry the trunk's graph).  Attention data
         # only exists when config.visualization is set (encoders.py:343-357): otherwise the reference returns None per
         # sub-layer and no probability tap is switched on.
         want_maps = bool(output_all_attention_masks and getattr(self.config, "visualization", False))
@@ -390,9 +395,14 @@ class BertForVLTasks(VLTasksModel):
         params = self._engine.param_list()
         self._engine.grad_mode = torch.is_grad_enabled()
         self._engine.tap_request = taps
+        diff_hs0 = diff_hs = None
         try:
-            x = TrunkFunction.apply(self._engine, self.training, input_txt, input_imgs, image_loc, token_type_ids,
-                                    attention_mask, image_attention_mask, *params)
+            if output_all_encoded_layers and self.differentiable_encoded_layers:
+                x, diff_hs0, diff_hs = differentiable_trunk(self._engine, self.training, input_txt, input_imgs, image_loc, token_type_ids,
+                                                  attention_mask, image_attention_mask, params)
+            else:
+                x = TrunkFunction.apply(self._engine, self.training, input_txt, input_imgs, image_loc, token_type_ids,
+                                        attention_mask, image_attention_mask, *params)
         finally:
             self._engine.tap_request = None  # (a call that failed before the engine took the request must not leave it behind)
         if self._engine.chunks_pending:  # a pipelined optimizer update: the heads' parameters are its last chunk
@@ -411,6 +421,11 @@ class BertForVLTasks(VLTasksModel):
             all_attention_mask = self._attention_data(taps if want_maps else None, input_txt.size(1))
         if output_all_encoded_layers:
             T = input_txt.size(1)
+            if diff_hs is not None:
+                # hidden state 0 is consumed by the stack's node as its text and box rows: their .grad is the whole gradient;
+                # the later ones are cut here, outside the node, and autograd assembles the [B,S,H] gradient of each
+                return (vil_prediction, None, None, all_attention_mask, [diff_hs0[0]] + [h[:, :T] for h in diff_hs],
+                        [diff_hs0[1]] + [h[:, T:] for h in diff_hs])
             hs = [taps["embed"]]
             for x1, out in zip(taps["x1"], taps["out"]):
                 hs += [x1, out]

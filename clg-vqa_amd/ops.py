@@ -280,6 +280,16 @@ def ln_bwd(dy, z, mean, rstd, gamma, dz, dpre16, dpre32, dgamma, dbeta, dbias, w
                                     float(p_pre), float(p_post), int(seed), orig_row_stride, _stream()), "vl_ln_bwd")
 
 
+def ln_bwd_add(dy, dy_add, z, mean, rstd, gamma, dz, dpre16, dpre32, dgamma, dbeta, dbias, ws, M, H, group=None, out_stride=0,
+               out_off=0, p_pre=0.0, p_post=0.0, seed=0, row_pre=None, row_post=None, orig_row_stride=1):
+    """ln_bwd of dy + dy_add (fp32, dy's layout; the sum is formed inside the kernel); dy_add None is ln_bwd."""
+    group = M if group is None else group
+    _lib.check(_lib.lib().vl_ln_bwd_add(_p(dy), _p(dy_add), _p(z), _p(mean), _p(rstd), _p(gamma), _p(row_pre), _p(row_post),
+                                        _p(dz), _p(dpre16), _p(dpre32), _p(dgamma), _p(dbeta), _p(dbias), _p(ws), M, H, group,
+                                        out_stride, out_off, float(p_pre), float(p_post), int(seed), orig_row_stride, _stream()),
+               "vl_ln_bwd_add")
+
+
 def ln_bwd_reduce(ws, M, H, dgamma, dbeta, dbias):
     """Column sums of the partials a ln_bwd(..., dgamma=None, dbeta=None, dbias=None) call left in ws."""
     _lib.check(_lib.lib().vl_ln_bwd_reduce(_p(ws), M, H, _p(dgamma), _p(dbeta), _p(dbias), _stream()), "vl_ln_bwd_reduce")

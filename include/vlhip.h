@@ -239,6 +239,16 @@ int vl_ln_bwd(const float* dy32, const float* z32, const float* mean, const floa
               const float* row_pre, const float* row_post, float* dz32, void* dpre16, float* dpre32, float* dgamma, float* dbeta, float* dbias,
               float* partial_ws, int64_t M, int64_t H, int64_t group, int64_t out_stride, int64_t out_off,
               float p_pre, float p_post, uint64_t seed, int64_t orig_row_stride, void* stream);
+/* vl_ln_bwd of the sum dy32 + dy_add: dy_add (fp32, 16-byte aligned, or NULL) has dy32's layout and is read through the same
+ * row map; the kernel forms fl(dy32 + dy_add) once on load and uses it wherever vl_ln_bwd uses dy32 (dz32, dpre16 / dpre32, the
+ * dgamma / dbeta / dbias partials), so the results are the bits of vl_ln_bwd on a pre-added tensor, without the pass over
+ * [M, H] that would add it.  dy_add = NULL launches the very kernel vl_ln_bwd launches.  The trunk uses it for gradients that
+ * reach a tapped hidden state from outside (VL_LY_TAP_GRAD_X1 / VL_LY_TAP_GRAD_OUT, the embedding output). */
+int vl_ln_bwd_add(const float* dy32, const float* dy_add, const float* z32, const float* mean, const float* rstd,
+                  const float* gamma, const float* row_pre, const float* row_post, float* dz32, void* dpre16, float* dpre32,
+                  float* dgamma, float* dbeta, float* dbias, float* partial_ws, int64_t M, int64_t H, int64_t group,
+                  int64_t out_stride, int64_t out_off, float p_pre, float p_post, uint64_t seed, int64_t orig_row_stride,
+                  void* stream);
 /* dgamma = dbeta = dbias = NULL makes vl_ln_bwd stop after the per-workgroup partials; this sums them later, on any
  * stream ordered after that call (the engine uses the weight-gradient stream: off the backward critical path). */
 int vl_ln_bwd_reduce(const float* partial_ws, int64_t M, int64_t H, float* dgamma, float* dbeta, float* dbias,
@@ -394,12 +404,17 @@ enum {
   VL_LY_EV_READY = 83, /* a hipEvent_t of the caller or 0: vl_stack_fwd makes its stream wait for it before the layer's first
                           kernel (the layer's parameters / prepared weights are being written on another stream: the optimizer
                           update of the previous step running under this forward) */
-  /* Optional per-layer taps of vl_stack_fwd (0 = off; caller-owned fp32 buffers; vl_stack_bwd ignores them): what
+  /* Optional per-layer taps of vl_stack_fwd (0 = off; caller-owned fp32 buffers; vl_stack_bwd does not read them): what
      BertEncoder.forward returns with output_all_encoded_layers / output_all_attention_masks (encoders.py:848-892).  Not
      allowed on a layer that runs in the pooled-row mode. */
   VL_LY_TAP_PROBS = 84, /* [B, nh, S, S]: the layer's attention goes through vl_qkv_attention_fwd_probs */
   VL_LY_TAP_X1 = 85,    /* [B*S, H]: output of LayerNorm 1 = the attention sub-layer's output */
   VL_LY_TAP_OUT = 86,   /* [B*S, H]: output of LayerNorm 2 = the feed-forward sub-layer's output */
+  /* Optional gradients of vl_stack_bwd with respect to the two hidden-state taps (0 = none; caller-owned fp32 [B*S, H], 16-byte
+     aligned): added to the gradient that flows down the stack at that point, inside the LayerNorm backward that reads it
+     (vl_ln_bwd_add).  TAP_GRAD_OUT of the top layer adds to VL_LY_DY.  Not allowed on a layer that runs in the pooled-row mode. */
+  VL_LY_TAP_GRAD_X1 = 87,   /* dL/d(TAP_X1): joins VL_LY_DX1 in the backward of LayerNorm 1 */
+  VL_LY_TAP_GRAD_OUT = 88,  /* dL/d(TAP_OUT): joins VL_LY_DY in the backward of LayerNorm 2 */
   VL_LY_FIELDS = 96
 };
 /* Pooled-row mode (VL_ST_POOLED_ONLY): the head reads hidden_states[:, 0] only (BertTextPooler, encoders.py:597-608; M3P
