@@ -12,104 +12,74 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VLHIP_LIBRARY") or os.path.join(_HERE, "csrc", "libvlhip.so")  # override: A/B builds
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlhip.h")
 
-P = c_void_p
-_SIGS = {
-    "vl_version": (c_int, []),
-    "vl_last_error": (c_char_p, []),
-    "vl_gemm_nt": (c_int, [P, P, c_int64, P, P, c_int64, c_int64, c_int64, c_int64, c_int, c_int, P, P, P, c_int64,
-                           P, P, P, c_int64, P]),
-    "vl_gemm_nt_ex": (c_int, [P, P, c_int64, P, P, c_int64, c_int64, c_int64, c_int64, c_int, c_int, P, P, P, c_int64,
-                              P, P, P, c_int64, P, P]),
-    "vl_gemm_small_ws_floats": (c_int64, [c_int64, c_int64, c_int64]),
-    "vl_gemm_nt_path": (c_int, [c_int64, c_int64, c_int64, c_int, c_int]),
-    "vl_gemm_splitk_plan": (c_int64, [c_int64, c_int64, c_int64]),
-    "vl_gemm_splitk_ws_floats": (c_int64, [c_int64, c_int64, c_int64]),
-    "vl_gemm_nt_splitk": (c_int, [P, c_int64, P, c_int64, c_int64, c_int64, c_int64, c_int64, P, P, P]),
-    "vl_gemm_tn_splitk": (c_int, [P, c_int64, P, c_int64, c_int64, c_int64, c_int64, c_int64, P, P, P]),
-    "vl_ln_bwd_reduce": (c_int, [P, c_int64, c_int64, P, P, P, P]),
-    "vl_ln_bwd_reduce2": (c_int, [P, c_int64, P, P, P, P, c_int64, P, P, P, c_int64, c_int, P]),
-    "vl_stack_desc_len": (c_int64, [c_int64]),
-    "vl_stack_fwd": (c_int, [P, c_int64, c_int64, P, P]),
-    "vl_stack_bwd": (c_int, [P, c_int64, c_int64, P, P]),
-    "vl_blocked_elems": (c_int64, [c_int64, c_int64]),
-    "vl_transpose_blocked": (c_int, [P, c_int64, c_int64, c_int64, P]),
-    "vl_colsum_finalize": (c_int, [P, c_int64, c_int64, P, c_int64, c_int, P]),
-    "vl_dw_grouped": (c_int, [P, c_int64, c_int64, c_int, P]),
-    "vl_dw_grouped_rowmajor": (c_int, [P, c_int64, c_int64, c_int, P]),
-    "vl_dw_grouped_mixed": (c_int, [P, c_int64, c_int64, c_int, c_int, P]),
-    "vl_dw_streamk_ws_bytes": (c_int64, [c_int64]),
-    "vl_dw_grouped_streamk": (c_int, [P, c_int64, c_int64, c_int, c_int, c_int64, P, c_int64, P]),
-    "vl_colreduce_multi": (c_int, [P, c_int64, c_int, P]),
-    "vl_qkv_attention_fwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int64, c_float,
-                                     c_uint64, P]),
-    "vl_qkv_attention_bwd": (c_int, [P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int64, c_float, c_uint64,
-                                     P]),
-    "vl_attn2_fwd": (c_int, [P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int64, c_float, c_uint64, P]),
-    "vl_attn2_fwd_probs": (c_int, [P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int64, c_float, c_uint64, P]),
-    "vl_qkv_attention_fwd_probs": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int64,
-                                           c_float, c_uint64, P]),
-    "vl_attn2_bwd": (c_int, [P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int64, c_float, c_uint64, P]),
-    "vl_ln_fwd": (c_int, [P, P, P, c_int64, P, P, P, P, c_float, P, P, P, P, P, c_int64, c_int64, c_int64, c_int64,
-                          c_int64, c_float, c_float, c_uint64, c_int64, c_int64, P]),
-    "vl_ln_fwd_rr": (c_int, [P, P, P, P, c_int64, P, P, P, P, c_float, P, P, P, P, P, c_int64, c_int64, c_int64, c_int64,
-                             c_int64, c_float, c_float, c_uint64, c_int64, c_int64, P]),
-    "vl_ln_bwd_ws_floats": (c_int64, [c_int64, c_int64]),
-    "vl_ln_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int64,
-                          c_float, c_float, c_uint64, c_int64, P]),
-    "vl_ln_bwd_add": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int64,
-                              c_float, c_float, c_uint64, c_int64, P]),
-    "vl_memset_zero": (c_int, [P, c_int64, P]),
-    "vl_gqa_loss_ws_bytes": (c_int64, [c_int64]),
-    "vl_gqa_loss": (c_int, [P, P, P, c_int64, c_int64, c_float, P, P, P, P]),
-    "vl_mask_mul": (c_int, [P, P, P, c_int64, P]),
-    "vl_weight_prep": (c_int, [P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, P]),
-    "vl_imp_ws_bytes": (c_int64, [c_int64]),
-    "vl_imp_select": (c_int, [P, P, P, c_int64, c_int64, P, P]),
-    "vl_weight_prep_multi": (c_int, [P, c_int64, c_int64, P]),
-    "vl_split_f32": (c_int, [P, P, P, c_int64, P]),
-    "vl_act_fwd": (c_int, [P, c_int64, c_int64, c_int, c_float, c_uint64, P, P, P, c_int64, P]),
-    "vl_act_bwd": (c_int, [P, P, c_int64, c_int64, c_int, c_float, c_uint64, P, P, c_int64, P]),
-    "vl_transpose_bf16": (c_int, [P, P, c_int64, c_int64, c_int64, c_int64, P]),
-    "vl_colsum_ws_floats": (c_int64, [c_int64, c_int64]),
-    "vl_colsum_bf16": (c_int, [P, c_int64, c_int64, c_int64, P, P, P]),
-    "vl_addmask": (c_int, [P, P, P, c_int64, c_int64, c_int64, P]),
-    "vl_embed_text_fwd": (c_int, [P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, P]),
-    "vl_embed_text_bwd": (c_int, [P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, P, P]),
-    "vl_embed_gather_fwd": (c_int, [P, P, P, c_int64, c_int64, P]),
-    "vl_embed_scatter_add": (c_int, [P, P, P, c_int64, c_int64, c_int64, P, P]),
-    "vl_loc_linear_fwd": (c_int, [P, P, P, P, c_int64, c_int64, c_int64, P]),
-    "vl_loc_linear_bwd": (c_int, [P, P, P, P, c_int64, c_int64, c_int64, P, P]),
-    "vl_loc_bwd_ws_floats": (c_int64, [c_int64, c_int64]),
-    "vl_loc_linear_bwd_input": (c_int, [P, P, P, c_int64, c_int64, c_int64, P]),
-    "vl_scatter_det_ws_bytes": (c_int64, [c_int64, c_int64, c_int64]),
-    "vl_scatter_add_det": (c_int, [P, c_int64, P, c_int64, c_int64, P, c_int64, P]),
-    "vl_adamw": (c_int, [P, P, P, P, c_int64, P, P, P, c_int64, c_float, c_float, c_float, c_int64, P, c_int, c_float,
-                         P, c_float, P, c_float, c_float, P, c_int, P, c_int64, c_int64, c_int64, P]),
-    "vl_sumsq_ws_floats": (c_int64, []),
-    "vl_sumsq": (c_int, [P, c_int64, P, P, P]),
-    "vl_sumsq_flagged": (c_int, [P, c_int64, P, P, c_int64, c_int64, c_int64, P, P]),
-}
+_SCALARS = {"int": c_int, "int64_t": c_int64, "uint64_t": c_uint64, "float": c_float}
+_header = _constants = None
+
+
+def _header_text():
+    """include/vlhip.h without its comments; read once per process."""
+    global _header
+    if _header is None:
+        with open(HEADER_PATH) as f:
+            _header = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    return _header
 
 
 def header_symbols():
     """Every function name declared in include/vlhip.h."""
-    with open(HEADER_PATH) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(vl_[a-z0-9_]+)\s*\(", text)))
+    return sorted(set(re.findall(r"\b(vl_[a-z0-9_]+)\s*\(", _header_text())))
 
 
 def header_constants():
     """{name: value} of the `NAME = value` enumerators and `#define NAME value` integer constants of include/vlhip.h
-    (descriptor field indices of vl_stack_*): the header is the single source of truth for the binding."""
-    with open(HEADER_PATH) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    out = {}
-    for name, val in re.findall(r"\b(VL_[A-Z0-9_]+)\s*=\s*(-?\d+)", text):
-        out[name] = int(val)
-    for name, val in re.findall(r"#define\s+(VL_[A-Z0-9_]+)\s+(0x[0-9a-fA-F]+|-?\d+)(?:ll)?\b", text):
-        out[name] = int(val, 0)
-    return out
+    (descriptor field indices of vl_stack_*, table widths, epilogue / activation codes): the header is the single source of
+    truth for the binding.  Parsed once; every call returns a dict of its own."""
+    global _constants
+    if _constants is None:
+        text, out = _header_text(), {}
+        for name, val in re.findall(r"\b(VL_[A-Z0-9_]+)\s*=\s*(-?\d+)", text):
+            out[name] = int(val)
+        for name, val in re.findall(r"#define\s+(VL_[A-Z0-9_]+)\s+(0x[0-9a-fA-F]+|-?\d+)(?:ll)?\b", text):
+            out[name] = int(val, 0)
+        _constants = out
+    return dict(_constants)
 
+
+def parse_signatures(text):
+    """{name: (restype, [argtypes])} of every `RET vl_name(args);` declaration of the comment-stripped header `text`: a
+    parameter with a `*` is a c_void_p, a scalar one must be of a type in _SCALARS, `(void)` is no arguments.  Raises
+    RuntimeError on whatever it does not understand -- a guessed binding would pass garbage to a kernel."""
+    text = re.sub(r'^\s*#.*$|extern\s+"C"\s*\{', "", text, flags=re.M)
+    sigs = {}
+    stmts = text.split(";")
+    for i, stmt in enumerate(stmts):
+        names = re.findall(r"\bvl_\w+", stmt)
+        if not names:
+            continue
+        m = i + 1 < len(stmts) and re.fullmatch(r"\s*([\w\s*]+?)\s*\b(vl_\w+)\s*\(([^()]*)\)\s*", stmt)
+        if not m:  # (what follows the last `;` is no declaration)
+            raise RuntimeError("clg_vqa_amd: cannot parse the declaration of %s in include/vlhip.h: %r"
+                               % (names[0], " ".join(stmt.split())))
+        ret, name, args = " ".join(m.group(1).split()), m.group(2), m.group(3).strip()
+        if ret != "const char*" and ret not in _SCALARS:
+            raise RuntimeError("clg_vqa_amd: %s in include/vlhip.h: unknown return type %r" % (name, ret))
+        argtypes = []
+        for arg in ([] if args == "void" else args.split(",")):
+            arg = " ".join(arg.split())
+            scalar = re.fullmatch(r"(?:const )?(\w+) \w+", arg)
+            if "*" in arg:
+                argtypes.append(c_void_p)
+            elif scalar is not None and scalar.group(1) in _SCALARS:
+                argtypes.append(_SCALARS[scalar.group(1)])
+            else:
+                raise RuntimeError("clg_vqa_amd: %s in include/vlhip.h: unknown parameter %r" % (name, arg))
+        if name in sigs:
+            raise RuntimeError("clg_vqa_amd: %s is declared twice in include/vlhip.h" % name)
+        sigs[name] = (c_char_p if ret == "const char*" else _SCALARS[ret], argtypes)
+    return sigs
+
+
+_SIGS = parse_signatures(_header_text())  # the whole binding: declaring an entry point in the header is all it takes
 
 _lib = None
 

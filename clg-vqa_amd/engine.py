@@ -23,10 +23,9 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from ._lib import header_constants
 from .ops import BF16, EPI_F32
 
-VL = header_constants()  # VL_ST_* / VL_LY_* descriptor field indices, parsed from include/vlhip.h
+VL = ops.C  # VL_ST_* / VL_LY_* descriptor field indices, parsed from include/vlhip.h
 
 
 def _ceil8(n):
@@ -998,6 +997,10 @@ class UC2Engine(EngineBase):
         return grads, dfeats, dlocs
 
 
+_RELEASED = ("clg_vqa_amd: the trunk's saved activations were released by its first backward "
+             "(retain_graph / double backward are not supported by the native trunk)")
+
+
 class TrunkFunction(torch.autograd.Function):
     """autograd boundary of a native trunk: (batch, *params) -> X_final [B,S,H], or its pooled rows [B,1,H] when the
     stack runs in the pooled-row mode (the heads only ever read X_final[:, 0])."""
@@ -1009,11 +1012,8 @@ class TrunkFunction(torch.autograd.Function):
         need_grad = engine.grad_mode and any(ctx.needs_input_grad)
         if need_grad:
             check_input_grads(engine.H, feats, locs, ctx.needs_input_grad[3], ctx.needs_input_grad[4])
-        ops.set_stream(torch.cuda.current_stream().cuda_stream)  # one stream lookup for all launches of the pass
-        try:
+        with ops.launching():  # one stream lookup for all launches of the pass
             out, sv = engine.forward(ids, feats, locs, seg, tmask, imask, training, need_grad=need_grad)
-        finally:
-            ops.set_stream(None)
         ctx.engine = engine
         ctx.sv = sv
         arena_claim(ctx, sv["arena"])
@@ -1022,14 +1022,12 @@ class TrunkFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dx):
         if ctx.sv is None:
-            raise RuntimeError("clg_vqa_amd: the trunk's saved activations were released by its first backward "
-                               "(retain_graph / double backward are not supported by the native trunk)")
-        ops.set_stream(torch.cuda.current_stream().cuda_stream)
+            raise RuntimeError(_RELEASED)
         try:
-            grads, dfeats, dlocs = ctx.engine.backward(ctx.sv, dx, want_feats=ctx.needs_input_grad[3],
-                                                       want_locs=ctx.needs_input_grad[4])
+            with ops.launching():
+                grads, dfeats, dlocs = ctx.engine.backward(ctx.sv, dx, want_feats=ctx.needs_input_grad[3],
+                                                           want_locs=ctx.needs_input_grad[4])
         finally:
-            ops.set_stream(None)
             ctx.engine.stack.join()
         ctx.sv = None
         needs = ctx.needs_input_grad[8:]
@@ -1040,10 +1038,6 @@ class TrunkFunction(torch.autograd.Function):
 # ------------------------------------------------------------------------------------------------------------------
 # differentiable hidden states (BertForVLTasks.differentiable_encoded_layers)
 # ------------------------------------------------------------------------------------------------------------------
-_RELEASED = ("clg_vqa_amd: the trunk's saved activations were released by its first backward "
-             "(retain_graph / double backward are not supported by the native trunk)")
-
-
 class TapCall(object):
     """What the two autograd nodes of one call with differentiable hidden states share: the trunk's output, the filled tap
     request, the saved activations (the arena is tied to the life of this object, like ``ctx`` of TrunkFunction)."""
@@ -1072,11 +1066,8 @@ class EmbedTapFunction(torch.autograd.Function):
         if need_grad:
             check_input_grads(engine.H, feats, locs, ctx.needs_input_grad[4], ctx.needs_input_grad[5])
         taps = engine.tap_request  # (engine.forward takes the request and fills it in place)
-        ops.set_stream(torch.cuda.current_stream().cuda_stream)
-        try:
+        with ops.launching():
             call.out, call.sv = engine.forward(ids, feats, locs, seg, tmask, imask, training, need_grad=need_grad)
-        finally:
-            ops.set_stream(None)
         call.taps, call.need_grad = taps, need_grad
         ctx.engine, ctx.call = engine, call
         arena_claim(call, call.sv["arena"])
@@ -1088,13 +1079,13 @@ class EmbedTapFunction(torch.autograd.Function):
         engine, call = ctx.engine, ctx.call
         if call.sv is None:
             raise RuntimeError(_RELEASED)
-        ops.set_stream(torch.cuda.current_stream().cuda_stream)
         try:
-            grads, dfeats, dlocs = engine.embed_backward(call.sv, _kernel_grad(d_t).view(-1, engine.H), [],
-                                                         want_feats=ctx.needs_input_grad[4], want_locs=ctx.needs_input_grad[5],
-                                                         dy_v=_kernel_grad(d_v).view(-1, engine.H))
+            with ops.launching():
+                grads, dfeats, dlocs = engine.embed_backward(call.sv, _kernel_grad(d_t).view(-1, engine.H), [],
+                                                             want_feats=ctx.needs_input_grad[4],
+                                                             want_locs=ctx.needs_input_grad[5],
+                                                             dy_v=_kernel_grad(d_v).view(-1, engine.H))
         finally:
-            ops.set_stream(None)
             engine.stack.join()
         call.sv = None
         grads = [g if need else None for g, need in zip(grads, ctx.needs_input_grad[9:])]
@@ -1130,12 +1121,11 @@ class StackTapFunction(torch.autograd.Function):
             dx, dout[-1] = dout[-1], None
         dx = torch.zeros(M, H, dtype=torch.float32, device=dev) if dx is None else _kernel_grad(dx)
         dx0 = torch.empty(M, H, dtype=torch.float32, device=dev)
-        ops.set_stream(torch.cuda.current_stream().cuda_stream)
         try:
-            dx0, layer_grads = engine.stack.backward(sv["arena"], sv["pw"]["layers"], dx.view(-1, H), sv["p_hid"], sv["p_att"],
-                                                     sv["seed0"], dtaps=(dx1, dout), dx0_out=dx0)
+            with ops.launching():
+                dx0, layer_grads = engine.stack.backward(sv["arena"], sv["pw"]["layers"], dx.view(-1, H), sv["p_hid"],
+                                                         sv["p_att"], sv["seed0"], dtaps=(dx1, dout), dx0_out=dx0)
         finally:
-            ops.set_stream(None)
             engine.stack.join()  # (autograd reads the weight gradients next: they are written on the side stream)
         call.stack_done = True
         grads = [g for lg in layer_grads for g in lg]

@@ -103,8 +103,7 @@ class HeadFunction(torch.autograd.Function):
         p = float(head.dropout.p) if training else 0.0
         seed = eng.last_seed(HEAD_SEED_SITE) if p > 0.0 else 0
         act = ACT_RELU if head.act == "relu" else ACT_TANH
-        ops.set_stream(torch.cuda.current_stream().cuda_stream)
-        try:
+        with ops.launching():
             split = eng.pooled_split(x)  # (hi, lo) [B, H] written by the trunk's last LayerNorm, when x is its output
             if split is None:
                 ops.split_f32(x[:, 0].contiguous(), ar.x_hi, ar.x_lo)
@@ -118,8 +117,6 @@ class HeadFunction(torch.autograd.Function):
                        ar.n_hi, ar.n_lo, ar.mean, ar.rstd, B, C)
             logits = torch.empty(B, NL, dtype=torch.float32, device=dev)
             ops.gemm_nt(ar.n_hi, ar.n_lo, pw2.hi, pw2.lo, B, NL, C, 3, EPI_F32, bias=pw2.bias, out32=logits)
-        finally:
-            ops.set_stream(None)
         if need_grad:
             ar.in_flight = True
             arena_claim(ctx, ar)
@@ -135,8 +132,7 @@ class HeadFunction(torch.autograd.Function):
         dev = dlogits.device
         f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
         NLp = _ceil64(NL)
-        ops.set_stream(torch.cuda.current_stream().cuda_stream)
-        try:
+        with ops.launching():
             # critical path: d(logits) -> d(pooled rows)
             ops.act_bwd(dlogits.contiguous(), None, B, NL, ACT_NONE, 0.0, 0, dz16=ar.dl16)
             ops.gemm_nt(ar.dl16, None, pw2.t_hi, None, B, C, pw2.Np, 1, EPI_F32, out32=ar.dn)
@@ -168,8 +164,6 @@ class HeadFunction(torch.autograd.Function):
                 dW2 = f32(NL, C)
                 ops.dw_grouped([(ar.t_dl, 0, NLp, ar.t_n, C, dW2, m2, NL, C), (ar.t_dz2, 0, C, ar.t_y1, P, dW1, m1, C, P),
                                 (ar.t_dz1, 0, P, ar.t_x, H, dWp, mp, P, H)], B)
-        finally:
-            ops.set_stream(None)
         ar.in_flight = False
         if len(ctx.x_shape) == 3 and ctx.x_shape[1] != 1:  # dense trunk output: only row 0 of a sample has a gradient
             dx = torch.zeros(ctx.x_shape, dtype=torch.float32, device=dev)

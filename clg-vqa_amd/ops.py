@@ -8,7 +8,10 @@ import torch
 from . import _lib
 
 BF16 = torch.bfloat16
-EPI_F32, EPI_GELU_SPLIT, EPI_DGELU_BF16, EPI_BF16, EPI_SPLIT = 0, 1, 2, 3, 4
+C = _lib.header_constants()  # enumerators and table widths of include/vlhip.h
+EPI_F32, EPI_GELU_SPLIT, EPI_DGELU_BF16, EPI_BF16, EPI_SPLIT = (
+    C["VL_EPI_F32"], C["VL_EPI_GELU_SPLIT"], C["VL_EPI_DGELU_BF16"], C["VL_EPI_BF16"], C["VL_EPI_SPLIT"])
+ACT_NONE, ACT_RELU, ACT_TANH, ACT_GELU = C["VL_ACT_NONE"], C["VL_ACT_RELU"], C["VL_ACT_TANH"], C["VL_ACT_GELU"]
 GEMM_TILE = 0  # default `tile` of gemm_nt (micro-benchmarks set it; the native stack always uses the automatic choice)
 
 
@@ -27,6 +30,23 @@ _launch = _Launch()
 def set_stream(handle, hold=None):
     """Route the native launches of this thread to `handle` (None = torch's current stream again)."""
     _launch.stream, _launch.hold = handle, hold
+
+
+class launching(object):
+    """``with ops.launching():`` routes this thread's native launches to `stream` (a HIP stream handle; default: torch's
+    current stream, looked up once on entry) and puts the previous routing back on the way out, exception or not."""
+
+    def __init__(self, stream=None, hold=None):
+        self.stream, self.hold = stream, hold
+
+    def __enter__(self):
+        self.prev = (_launch.stream, _launch.hold)
+        set_stream(torch.cuda.current_stream().cuda_stream if self.stream is None else self.stream, self.hold)
+        return self
+
+    def __exit__(self, *exc):
+        set_stream(*self.prev)
+        return False
 
 
 def _stream():
@@ -104,21 +124,21 @@ def gemm_nt(a_hi, a_lo, b_hi, b_lo, M, N, K, passes, epilogue, bias=None, resid=
     L = _lib.lib()
     tile = tile or GEMM_TILE
     st = _stream()
-    extra = (ctypes.c_int64 * 8)()
-    extra[0] = tile
-    extra[7] = persist  # > 0: persistent form of the ping-pong kernel on that many workgroups (VL_GX_PERSIST)
+    extra = (ctypes.c_int64 * C["VL_GX_FIELDS"])()
+    extra[C["VL_GX_TILE"]] = tile
+    extra[C["VL_GX_PERSIST"]] = persist  # > 0: persistent form of the ping-pong kernel on that many workgroups
     if M <= 8192 and tile in (0, 8) and colsum is None and (SMALL_GEMM or tile == 8):
         nws = L.vl_gemm_small_ws_floats(M, N, K)
-        extra[1], extra[2] = small_ws(a_hi.device, nws, st).data_ptr(), nws
+        extra[C["VL_GX_WS"]], extra[C["VL_GX_WS_FLOATS"]] = small_ws(a_hi.device, nws, st).data_ptr(), nws
     if image is not None:
-        extra[3], extra[4] = _p(image), image_cols or N
+        extra[C["VL_GX_IMG"]], extra[C["VL_GX_IMG_COLS"]] = _p(image), image_cols or N
     if colsum is not None:
         assert colsum.shape[1] == N
-        extra[5] = _p(colsum)
+        extra[C["VL_GX_COLSUM"]] = _p(colsum)
     _lib.check(L.vl_gemm_nt_ex(pa, pal, lda, pb, pbl, ldb, M, N, K, passes, epilogue, _p(bias),
                                _pld(resid)[0] if resid is not None else None, po32, ldc, ph, pl, px, ld16,
-                               ctypes.cast(extra, ctypes.c_void_p), st), "vl_gemm_nt")
-    return int(extra[6])
+                               ctypes.cast(extra, ctypes.c_void_p), st), "vl_gemm_nt_ex")
+    return int(extra[C["VL_GX_COLSUM_ROWS"]])
 
 
 def gemm_nt_splitk(a_hi, b_hi, M, N, K, out32, splits=None):
@@ -166,7 +186,8 @@ def stack_bwd(desc, layer_hi, layer_lo, stream_main, stream_side):
 
 def transpose_blocked(entries, M, max_blocks=0):
     """entries = [(src [M,N] bf16 (row-major, ld = stride(0)), dst blocked image, colsum_partial or None), ...]"""
-    arr = _table(6, [_pld(src) + (src.shape[1], _p(dst), 0 if cs is None else _p(cs), 0) for src, dst, cs in entries])
+    arr = _table(C["VL_TR_FIELDS"], [_pld(src) + (src.shape[1], _p(dst), 0 if cs is None else _p(cs), 0)
+                                     for src, dst, cs in entries])
     _lib.check(_lib.lib().vl_transpose_blocked(ctypes.cast(arr, ctypes.c_void_p), len(entries), M, max_blocks, _stream()),
                "vl_transpose_blocked")
 
@@ -179,8 +200,9 @@ def colsum_finalize(partial, nblk, N, outs, accumulate=False):
 
 def colreduce_multi(sets, accumulate=False):
     """sets = [(src [nrows, ncols] fp32, seg, (out0, out1, out2) with None = skip), ...] (<= 4): one launch."""
-    arr = _table(8, [[_p(src), src.shape[0], src.shape[1], seg] + [0 if t is None else _p(t) for t in outs]
-                     + [0] * (4 - len(outs)) for src, seg, outs in sets])
+    width = C["VL_CR_FIELDS"]
+    arr = _table(width, [[_p(src), src.shape[0], src.shape[1], seg] + [0 if t is None else _p(t) for t in outs]
+                         + [0] * (width - 4 - len(outs)) for src, seg, outs in sets])
     _lib.check(_lib.lib().vl_colreduce_multi(ctypes.cast(arr, ctypes.c_void_p), len(sets), 1 if accumulate else 0,
                                              _stream()), "vl_colreduce_multi")
 
@@ -193,8 +215,9 @@ def dw_grouped(problems, K, accumulate=False):
         assert out.dtype == torch.float32 and out.stride(1) == 1
         rows.append([_p(aT) + 2 * 64 * a_row0, a_rows, _p(bT), b_rows, out.data_ptr(), out.stride(0),
                      0 if mask is None else _p(mask), M, N, 0])
-    _lib.check(_lib.lib().vl_dw_grouped(ctypes.cast(_table(10, rows), ctypes.c_void_p), len(rows), K, 1 if accumulate else 0,
-                                        _stream()), "vl_dw_grouped")
+    arr = _table(C["VL_DW_FIELDS"], rows)
+    _lib.check(_lib.lib().vl_dw_grouped(ctypes.cast(arr, ctypes.c_void_p), len(rows), K, 1 if accumulate else 0, _stream()),
+               "vl_dw_grouped")
 
 
 def dw_grouped_rowmajor(problems, rows, accumulate=False):
@@ -205,8 +228,9 @@ def dw_grouped_rowmajor(problems, rows, accumulate=False):
         assert out.dtype == torch.float32 and out.stride(1) == 1
         tab.append(_pld(dy) + _pld(x) + (out.data_ptr(), out.stride(0), 0 if mask is None else _p(mask), M, N,
                                          0 if cs is None else _p(cs)))
-    _lib.check(_lib.lib().vl_dw_grouped_rowmajor(ctypes.cast(_table(10, tab), ctypes.c_void_p), len(tab), rows,
-                                                 1 if accumulate else 0, _stream()), "vl_dw_grouped_rowmajor")
+    arr = _table(C["VL_DW_FIELDS"], tab)
+    _lib.check(_lib.lib().vl_dw_grouped_rowmajor(ctypes.cast(arr, ctypes.c_void_p), len(tab), rows, 1 if accumulate else 0,
+                                                 _stream()), "vl_dw_grouped_rowmajor")
 
 
 def dw_grouped_mixed(problems, rows, mode, accumulate=False, budget=0, ws=None):
@@ -214,9 +238,10 @@ def dw_grouped_mixed(problems, rows, mode, accumulate=False, budget=0, ws=None):
     None) when its mode bit is set (bit 0: dY, bit 1: X), else its K-major image (1-D tensor) with the image's column count.
     budget > 0: the stream-K form on that many workgroups with the zero-initialised workspace `ws` (dw_streamk_ws)."""
     n = len(problems)
-    arr = _table(10, [(_pld(a) if mode & 1 else (_p(a), a_cols)) + (_pld(b) if mode & 2 else (_p(b), b_cols))
-                      + (out.data_ptr(), out.stride(0), 0 if mask is None else _p(mask), M, N, 0 if cs is None else _p(cs))
-                      for a, a_cols, b, b_cols, out, mask, M, N, cs in problems])
+    tab = [(_pld(a) if mode & 1 else (_p(a), a_cols)) + (_pld(b) if mode & 2 else (_p(b), b_cols))
+           + (out.data_ptr(), out.stride(0), 0 if mask is None else _p(mask), M, N, 0 if cs is None else _p(cs))
+           for a, a_cols, b, b_cols, out, mask, M, N, cs in problems]
+    arr = _table(C["VL_DW_FIELDS"], tab)
     if budget:
         _lib.check(_lib.lib().vl_dw_grouped_streamk(ctypes.cast(arr, ctypes.c_void_p), n, rows, 1 if accumulate else 0, mode,
                                                     int(budget), _p(ws), ws.numel() * ws.element_size(), _stream()),
@@ -264,7 +289,7 @@ def ln_fwd(y, resid, addvec, gamma, beta, eps, out32, out_hi, out_lo, mean, rstd
                                        _p(beta), float(eps), _p(out32),
                                        _p(out_hi), _p(out_lo), _p(mean), _p(rstd), M, H, group, out_stride, out_off,
                                        float(p_pre), float(p_post), int(seed), orig_row_stride, resid_row_stride, _stream()),
-               "vl_ln_fwd")
+               "vl_ln_fwd_rr")
 
 
 def ln_bwd_ws(M, H, device):
@@ -341,9 +366,6 @@ def imp_select(w_flat, mask_flat, new_mask_flat, k):
 
 def weight_prep_multi(table_dev, ndesc, total_tiles):
     _lib.check(_lib.lib().vl_weight_prep_multi(_p(table_dev), ndesc, total_tiles, _stream()), "vl_weight_prep_multi")
-
-
-ACT_NONE, ACT_RELU, ACT_TANH, ACT_GELU = 0, 1, 2, 3
 
 
 def act_fwd(z32, M, N, act, p_drop, seed, out32=None, out_hi=None, out_lo=None):
@@ -445,7 +467,7 @@ def scatter_add_det(tables, dz32, R, H):
     for ids, kind, table, skip, flags, T in tables:
         assert ids.is_contiguous() and ids.dtype == torch.int64 and table.is_contiguous() and table.dtype == torch.float32
         rows.append([_p(ids), kind, _p(table), skip, 0 if flags is None else _p(flags), T])
-    arr = _table(6, rows)
+    arr = _table(C["VL_SC_FIELDS"], rows)
     L = _lib.lib()
     nbytes = L.vl_scatter_det_ws_bytes(n, R, H)
     ws = _ws("scatter", dz32.device, nbytes)

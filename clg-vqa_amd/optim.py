@@ -373,25 +373,21 @@ class FusedAdamW(object):
         upd.wait_event(self._ev_start)
         lr_mult = self.lr_mult()
         flags = self._flag_args()
-        ops.set_stream(upd.cuda_stream)
-        try:
-            with torch.cuda.stream(upd):
-                first = True
-                for c, ch in enumerate(chunks):
-                    if ch is not None:
-                        lo, hi, i, j, seg_end = ch
-                        fl = {}
-                        if flags and lo <= flags["flag_begin"] < hi:
-                            fl = dict(flags, flag_begin=flags["flag_begin"] - lo)
-                        ops.adamw(a.param[lo:hi], a.grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], seg_end,
-                                  self.seg_lr[i:j], self.seg_wd[i:j], self.betas[0], self.betas[1], self.eps, self.opt_step,
-                                  self.correct_bias, lr_mult, sumsq_next=nxt if first else None,
-                                  seg_step=None if seg_step is None else seg_step[i:j], **kw, **fl)
-                        first = False
-                    eng.prepare_chunk(c)
-                    eng.chunk_events[c].record(upd)
-        finally:
-            ops.set_stream(None)
+        with ops.launching(upd.cuda_stream), torch.cuda.stream(upd):
+            first = True
+            for c, ch in enumerate(chunks):
+                if ch is not None:
+                    lo, hi, i, j, seg_end = ch
+                    fl = {}
+                    if flags and lo <= flags["flag_begin"] < hi:
+                        fl = dict(flags, flag_begin=flags["flag_begin"] - lo)
+                    ops.adamw(a.param[lo:hi], a.grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], seg_end,
+                              self.seg_lr[i:j], self.seg_wd[i:j], self.betas[0], self.betas[1], self.eps, self.opt_step,
+                              self.correct_bias, lr_mult, sumsq_next=nxt if first else None,
+                              seg_step=None if seg_step is None else seg_step[i:j], **kw, **fl)
+                    first = False
+                eng.prepare_chunk(c)
+                eng.chunk_events[c].record(upd)
         if hasattr(self.model, "mark_weights_dirty"):
             self.model.mark_weights_dirty()  # (module-level Linears outside the engine re-prepare themselves)
         eng.finish_prepare()

@@ -20,6 +20,9 @@ def test_library_exports_every_declared_symbol():
     for n in names:
         assert hasattr(handle, n), n
     assert set(names) == set(_lib._SIGS), "python binding table out of sync with include/vlhip.h"
+    for n in names:  # the loaded functions carry the signatures parsed from the header (tests/test_binding_host.py pins those)
+        fn = getattr(_lib.lib(), n)
+        assert fn.restype is _lib._SIGS[n][0] and list(fn.argtypes) == _lib._SIGS[n][1], n
     assert _lib.lib().vl_version() == 100
 
 

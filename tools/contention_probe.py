@@ -56,10 +56,9 @@ def main():
             torch.cuda.synchronize()
             if budget is not None:
                 side.wait_stream(torch.cuda.current_stream())
-                ops.set_stream(side.cuda_stream)
-                for _ in range(2):  # two layers' worth: the dW stream is busy for the whole measurement
-                    ops.dw_grouped_mixed(probs, M, 3, budget=budget, ws=ws)
-                ops.set_stream(None)
+                with ops.launching(side.cuda_stream):
+                    for _ in range(2):  # two layers' worth: the dW stream is busy for the whole measurement
+                        ops.dw_grouped_mixed(probs, M, 3, budget=budget, ws=ws)
                 torch.cuda._sleep(200000)  # let the weight-gradient workgroups take their CUs first
             ev = dx_products(tile_wide)
             torch.cuda.synchronize()
