@@ -507,3 +507,35 @@ def sumsq(x, out, row_flags=None, flag_begin=0, flag_rows=0, flag_row_len=0, ws=
     else:
         _lib.check(_lib.lib().vl_sumsq_flagged(_p(x), x.numel(), _p(out), _p(row_flags), flag_begin, flag_rows,
                                                flag_row_len, _p(ws), _stream()), "vl_sumsq_flagged")
+
+
+def collate_regions(feats_packed, boxes_packed, row_off, whp, feats, loc, image_mask, normalize=False):
+    """Packed region rows [n_rows, F] / boxes [n_rows, 4] + row_off [B+1] + whp [B, 3] -> feats [B, V, F], loc [B, V, L],
+    image_mask [B, V] int64 (csrc/collate.hip); normalize: M3P norm_embeddings."""
+    B, V, F = feats.shape
+    n_rows = feats_packed.shape[0]
+    assert loc.shape[:2] == (B, V) and image_mask.shape == (B, V) and row_off.numel() == B + 1 and whp.shape == (B, 3)
+    assert feats_packed.shape == (n_rows, F) and boxes_packed.shape == (n_rows, 4)
+    # (a batch without a single box has empty sections, which torch hands out as null pointers: nothing is read from them)
+    pf, pb = (_p(feats_packed), _p(boxes_packed)) if n_rows else (_p(row_off), _p(row_off))
+    _lib.check(_lib.lib().vl_collate_regions(pf, pb, _p(row_off), _p(whp), _p(feats), _p(loc), _p(image_mask), B, V, F,
+                                             loc.shape[2], n_rows, int(bool(normalize)), _stream()), "vl_collate_regions")
+
+
+def collate_text(tok, tok_off, ids, input_mask, segment_ids, pad_id):
+    """Packed token ids + tok_off [B+1] -> ids / input_mask / segment_ids [B, T] int64 (truncation keeps the last token)."""
+    B, T = ids.shape
+    assert input_mask.shape == (B, T) and segment_ids.shape == (B, T) and tok_off.numel() == B + 1
+    _lib.check(_lib.lib().vl_collate_text(_p(tok), _p(tok_off), _p(ids), _p(input_mask), _p(segment_ids), B, T, int(pad_id),
+                                          tok.numel(), _stream()), "vl_collate_text")
+
+
+def collate_targets(labels, scores, prior32, target, dist):
+    """labels / scores [B, Lb] (+ the fp32 [C, C] prior table or None) -> target [B, C] (scatter) and dist [B, C] (the prior
+    row of each sample's last label; zeros without a table)."""
+    B, Lb = labels.shape
+    Cn = target.shape[1]
+    assert scores.shape == (B, Lb) and target.shape == (B, Cn) and dist.shape == (B, Cn)
+    assert prior32 is None or prior32.shape == (Cn, Cn)
+    _lib.check(_lib.lib().vl_collate_targets(_p(labels), _p(scores), _p(prior32), _p(target), _p(dist), B, Lb, Cn, _stream()),
+               "vl_collate_targets")

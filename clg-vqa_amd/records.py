@@ -97,3 +97,172 @@ def collate_records(records, seq_len, region_len, num_locs, num_labels, padding_
     return (torch.from_numpy(feats), torch.from_numpy(loc.astype(np.float32)), torch.from_numpy(image_mask),
             torch.from_numpy(ids), target, torch.from_numpy(input_mask), torch.zeros((B, seq_len), dtype=torch.int64),
             qid, torch.tensor(batch_index), dist)
+
+
+# ---- record -> batch on the device (csrc/collate.hip) ------------------------------------------
+# The host writes every record ONCE, ragged, into one pinned blob; one copy takes the blob to HBM; three kernels pad it
+# into the same 10-tuple and do the arithmetic above (box locations, norm_embeddings, truncation, target scatter, prior
+# row gather) there.  ``collate_records`` stays as it is: it is the yardstick of the device path.
+
+PACK_ALIGN = 256  # every section of the blob starts on a 256-byte boundary
+# section -> (dtype, trailing shape as a function of the batch's sizes); in blob order
+_SECTIONS = (("feats", np.float32), ("boxes", np.float32), ("row_off", np.int64), ("whp", np.float32), ("tok", np.int64),
+             ("tok_off", np.int64), ("labels", np.int64), ("scores", np.float32), ("qid", np.int64))
+
+
+def _section_shapes(B, n_rows, n_tok, Lb, feat_dim):
+    return {"feats": (n_rows, feat_dim), "boxes": (n_rows, 4), "row_off": (B + 1,), "whp": (B, 3), "tok": (n_tok,),
+            "tok_off": (B + 1,), "labels": (B, Lb), "scores": (B, Lb), "qid": (B,)}
+
+
+_pack_pools = {}  # threads -> ThreadPoolExecutor of the feature copy (numpy releases the GIL while it copies)
+
+
+def _copy_rows(dst, parts, offs, threads):
+    """dst[offs[j]:offs[j+1]] = parts[j] for every j, split over `threads` threads."""
+    def work(k):
+        for j in range(k, len(parts), threads):
+            dst[offs[j]:offs[j + 1]] = parts[j]
+    if threads <= 1 or len(parts) < 2 * threads:
+        for j in range(len(parts)):
+            dst[offs[j]:offs[j + 1]] = parts[j]
+        return
+    pool = _pack_pools.get(threads)
+    if pool is None:
+        from concurrent.futures import ThreadPoolExecutor
+        pool = _pack_pools[threads] = ThreadPoolExecutor(threads, thread_name_prefix="pack_records")
+    list(pool.map(work, range(threads)))
+
+
+def pack_records(records, seq_len, region_len, num_locs, num_labels, feat_dim=2048, batch_index=0, out=None, threads=1):
+    """The record dicts of ``collate_records`` -> ``(blob, meta)``: one ``uint8`` blob (pinned when a GPU is present; pass
+    the previous blob of a prefetch slot as ``out`` and it is reused when large enough) holding the sections
+
+        feats [N, F] f32 | boxes [N, 4] f32 | row_off [B+1] i64 | whp [B, 3] f32 | tok [sum len] i64 | tok_off [B+1] i64 |
+        labels [B, Lb] i64 | scores [B, Lb] f32 | qid [B] i64          (N = sum of the box counts)
+
+    each on a 256-byte boundary, and ``meta``: ``offsets`` (section -> byte offset), ``nbytes``, ``B``, ``n_rows``,
+    ``n_tok``, ``Lb``, ``feat_dim``, ``batch_index``.  No arithmetic on features or boxes: only ``whp`` = {fl32(w), fl32(h),
+    fl32(double(w) * double(h))}, the three scalars ``box_locations`` rounds on the host.  Raises ValueError for what a
+    kernel must never see: more than ``region_len`` boxes, fewer than 2 tokens, a label outside [0, num_labels), label
+    lists of unequal length, a feature row length other than ``feat_dim``.  A record with 0 boxes is legal.
+    ``threads`` > 1 splits the one pass over the features (record -> blob) over that many threads."""
+    B = len(records)
+    if B < 1:
+        raise ValueError("pack_records: an empty batch")
+    if seq_len < 2 or not 4 <= num_locs <= 8:
+        raise ValueError("pack_records: need seq_len >= 2 and 4 <= num_locs <= 8")
+    feats, boxes, toks = [], [], []
+    row_off = np.zeros(B + 1, dtype=np.int64)
+    tok_off = np.zeros(B + 1, dtype=np.int64)
+    w64 = np.empty(B, dtype=np.float64)
+    h64 = np.empty(B, dtype=np.float64)
+    Lb = len(records[0]["labels"])
+    if Lb < 1:
+        raise ValueError("pack_records: a record needs at least one label")
+    labels = np.empty((B, Lb), dtype=np.int64)
+    scores = np.empty((B, Lb), dtype=np.float32)
+    qid = np.empty(B, dtype=np.int64)
+    for b, r in enumerate(records):
+        bx = np.asarray(r["boxes"], dtype=np.float32).reshape(-1, 4)
+        n = len(bx)
+        if n > region_len:
+            raise ValueError("pack_records: record %d has %d boxes, region_len is %d" % (b, n, region_len))
+        f = np.asarray(r["features"], dtype=np.float32)
+        if n == 0 and f.size == 0:
+            f = f.reshape(0, feat_dim)
+        if f.ndim != 2 or f.shape[1] != feat_dim:
+            raise ValueError("pack_records: record %d: feature rows of shape %s, feat_dim is %d" % (b, f.shape, feat_dim))
+        if f.shape[0] != n:
+            raise ValueError("pack_records: record %d: %d feature rows for %d boxes" % (b, f.shape[0], n))
+        t = np.asarray(r["tokens"], dtype=np.int64).reshape(-1)
+        if len(t) < 2:
+            raise ValueError("pack_records: record %d has %d tokens (need <s> ... </s>: at least 2)" % (b, len(t)))
+        lab = np.asarray(r["labels"], dtype=np.int64).reshape(-1)
+        sc = np.asarray(r["scores"], dtype=np.float32).reshape(-1)
+        if len(lab) != Lb or len(sc) != Lb:
+            raise ValueError("pack_records: record %d has %d labels / %d scores, record 0 has %d" % (b, len(lab), len(sc), Lb))
+        feats.append(f)
+        boxes.append(bx)
+        toks.append(t)
+        row_off[b + 1] = row_off[b] + n
+        tok_off[b + 1] = tok_off[b] + len(t)
+        w64[b], h64[b] = float(r["img_w"]), float(r["img_h"])
+        labels[b], scores[b], qid[b] = lab, sc, int(r["question_id"])
+    bad = np.nonzero(((labels < 0) | (labels >= num_labels)).any(1))[0]
+    if len(bad):
+        raise ValueError("pack_records: record %d: label outside [0, %d)" % (bad[0], num_labels))
+    n_rows, n_tok = int(row_off[-1]), int(tok_off[-1])
+    shapes = _section_shapes(B, n_rows, n_tok, Lb, feat_dim)
+    offsets, pos = {}, 0
+    for name, dt in _SECTIONS:
+        offsets[name] = pos
+        pos += int(np.prod(shapes[name])) * np.dtype(dt).itemsize
+        pos = (pos + PACK_ALIGN - 1) // PACK_ALIGN * PACK_ALIGN
+    nbytes = pos
+    if out is None or out.numel() < nbytes:
+        # (grow with headroom: a ragged stream's blobs differ in size from batch to batch)
+        cap = nbytes if out is None else max(nbytes, 2 * out.numel())
+        out = torch.empty(cap, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    meta = dict(offsets=offsets, nbytes=nbytes, B=B, n_rows=n_rows, n_tok=n_tok, Lb=Lb, feat_dim=feat_dim,
+                batch_index=int(batch_index))
+    v = {k: t.numpy() for k, t in packed_views((out, meta)).items()}
+    if n_rows:
+        _copy_rows(v["feats"], feats, row_off, threads)  # the one pass over the features: record -> blob
+        np.concatenate(boxes, axis=0, out=v["boxes"])
+    np.concatenate(toks, out=v["tok"])
+    v["row_off"][:], v["tok_off"][:] = row_off, tok_off
+    v["whp"][:, 0], v["whp"][:, 1], v["whp"][:, 2] = w64, h64, w64 * h64  # rounded to fp32 by the assignment
+    v["labels"][:], v["scores"][:], v["qid"][:] = labels, scores, qid
+    return out, meta
+
+
+def packed_views(packed):
+    """``(blob, meta)`` (host or device blob) -> {section: typed tensor view of the blob}."""
+    blob, meta = packed
+    shapes = _section_shapes(meta["B"], meta["n_rows"], meta["n_tok"], meta["Lb"], meta["feat_dim"])
+    out = {}
+    for name, dt in _SECTIONS:
+        shape = shapes[name]
+        n = int(np.prod(shape)) * np.dtype(dt).itemsize
+        o = meta["offsets"][name]
+        tdt = torch.float32 if dt is np.float32 else torch.int64
+        out[name] = blob[o:o + n].view(tdt).view(shape)
+    return out
+
+
+def prior_table_device(T, device):
+    """The dense fp64 table of ``prior_table`` as the fp32 device table the collate kernel gathers rows from (cast once: the
+    reference casts every gathered row to fp32; 13.6 MB at 1842 labels)."""
+    return torch.from_numpy(np.ascontiguousarray(T, dtype=np.float64)).to(torch.float32).to(device).contiguous()
+
+
+def collate_on_device(packed_dev, seq_len, region_len, num_locs, num_labels, padding_index=1, norm_embeddings=False,
+                      prior32=None):
+    """``packed_dev``: ``(blob on the device, meta)`` of ``pack_records``.  Three native launches on the current launch
+    stream (``ops.launching``) -> the 10-tuple of ``collate_records`` on the device: same order, shapes and dtypes
+    (``ix`` the 0-dim ``batch_index`` tensor).  Bit-equal to ``collate_records`` except the L2-normalised features of
+    ``norm_embeddings``, which are within 2 * 2^-24 relative of the exact quotient (torch's CPU result is ~4 * 2^-24 off)."""
+    from . import ops
+    blob, meta = packed_dev
+    if not blob.is_cuda:
+        raise RuntimeError("clg_vqa_amd.records.collate_on_device: the blob must be on the MI355X (no CPU path; the host "
+                           "routine is collate_records)")
+    dev, B, F = blob.device, meta["B"], meta["feat_dim"]
+    if prior32 is not None and (prior32.dtype != torch.float32 or tuple(prior32.shape) != (num_labels, num_labels)):
+        raise ValueError("collate_on_device: prior32 must be the fp32 [num_labels, num_labels] table of prior_table_device")
+    v = packed_views(packed_dev)
+    f32, i64 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int64, device=dev)
+    feats = torch.empty((B, region_len, F), **f32)
+    loc = torch.empty((B, region_len, num_locs), **f32)
+    image_mask = torch.empty((B, region_len), **i64)
+    ids = torch.empty((B, seq_len), **i64)
+    input_mask = torch.empty((B, seq_len), **i64)
+    segment_ids = torch.empty((B, seq_len), **i64)
+    target = torch.empty((B, num_labels), **f32)
+    dist = torch.empty((B, num_labels), **f32)
+    ops.collate_regions(v["feats"], v["boxes"], v["row_off"], v["whp"], feats, loc, image_mask, norm_embeddings)
+    ops.collate_text(v["tok"], v["tok_off"], ids, input_mask, segment_ids, padding_index)
+    ops.collate_targets(v["labels"], v["scores"], prior32, target, dist)
+    ix = torch.full((), meta["batch_index"], dtype=torch.int64, device=dev)
+    return (feats, loc, image_mask, ids, target, input_mask, segment_ids, v["qid"], ix, dist)

@@ -68,6 +68,38 @@ def make_batch(batch_size, seq_len=20, num_boxes=36, num_labels=1842, vocab_size
             torch.arange(B, dtype=torch.int64), torch.arange(B, dtype=torch.int64), t(dist))
 
 
+def make_records(batch_size, seq_len=20, num_boxes=36, num_labels=1842, vocab_size=250002, feat_dim=2048, seed=1234,
+                 box_counts=None, token_counts=None, labels_per_record=1):
+    """``batch_size`` ragged synthetic RECORDS (the dicts ``records.collate_records`` / ``records.pack_records`` take): a
+    pure function of its arguments.
+
+    Box lists are full (``num_boxes``), short and empty; token lists short (2 tokens: ``<s> </s>``), ordinary and
+    over-long (``seq_len + 3``: truncated by the collate); ``box_counts`` / ``token_counts`` (sequences, cycled) override
+    the pattern.  features: relu(randn) * 1.5 like ``make_batch``; boxes: pixel (x1, y1, x2, y2) inside a random
+    ``img_w`` x ``img_h`` image; ``labels_per_record`` distinct labels each, scores 1, 1/2, 1/3, ..."""
+    rs = np.random.RandomState(seed)
+    T, V = seq_len, num_boxes
+    out = []
+    for b in range(batch_size):
+        short_n = int(rs.randint(1, max(V, 2)))
+        mid_t = int(rs.randint(min(3, T), T + 1))
+        n = int(box_counts[b % len(box_counts)]) if box_counts is not None else (V, short_n, 0, V)[b % 4]
+        nt = int(token_counts[b % len(token_counts)]) if token_counts is not None else (mid_t, 2, T + 3)[b % 3]
+        img_w, img_h = int(rs.randint(320, 641)), int(rs.randint(240, 481))
+        feats = (np.maximum(rs.randn(n, feat_dim), 0.0) * 1.5).astype(np.float32)
+        x1 = rs.uniform(0, 0.7, size=n) * img_w
+        y1 = rs.uniform(0, 0.7, size=n) * img_h
+        bw = rs.uniform(0.05, 0.3, size=n) * img_w
+        bh = rs.uniform(0.05, 0.3, size=n) * img_h
+        boxes = np.stack([x1, y1, x1 + bw, y1 + bh], axis=-1).astype(np.float32).reshape(n, 4)
+        tokens = [0] + rs.randint(5, vocab_size, size=nt - 2).tolist() + [2]
+        labels = rs.choice(num_labels, size=labels_per_record, replace=False).astype(np.int64)
+        scores = (1.0 / np.arange(1, labels_per_record + 1)).astype(np.float32)
+        out.append(dict(features=feats, boxes=boxes, img_w=img_w, img_h=img_h, tokens=tokens, labels=labels.tolist(),
+                        scores=scores.tolist(), question_id=int(rs.randint(0, 2 ** 31 - 1))))
+    return out
+
+
 def seeded_tensor(name, shape, seed=0, std=0.02):
     """Deterministic N(0, std) tensor that depends only on (name, shape, seed)."""
     rs = np.random.RandomState((zlib.crc32(name.encode()) + 7919 * seed) & 0x7FFFFFFF)

@@ -517,6 +517,42 @@ int vl_scatter_add_det(const int64_t* tab, int64_t n, const float* dz32, int64_t
                        void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Record -> batch on the device (csrc/collate.hip): the padding and the arithmetic of the reference's per-sample Python
+ * preprocessing, from the ragged sections of one packed blob (clg_vqa_amd/records.py::pack_records) that a single copy
+ * brought to HBM.  Replaces volta/volta/datasets/gqa_dataset_semantic_code_mix.py:564-651 (BertPreprocessBatch.__call__:
+ * box-location features, norm_embeddings, token truncation and padding), :386-452 (GQAClassificationLoader.__iter__: the
+ * target scatter and the padded batch tensors) and :371-381 (get_embeddingdist).  Streaming kernels, no atomics, one writer
+ * and one fixed order of operations per output element: two calls give the same bits.  Every output element is written
+ * (padding included), nothing outside the stated shapes is.
+ *
+ * vl_collate_regions: feats_packed [n_rows, F] / boxes_packed [n_rows, 4] fp32 (pixel x1 y1 x2 y2), the records' rows
+ *   concatenated; row_off [B+1] int64 prefix sums of the box counts n_b (0 <= n_b <= V: the caller's duty, rows outside
+ *   [0, n_rows) are treated as padding); whp [B, 3] fp32 {fl32(w), fl32(h), fl32(double(w) * double(h))}.
+ *   -> feats [B, V, F], loc [B, V, L], image_mask [B, V] int64.  Row v of sample b is live when v < n_b: its features are
+ *   copied, a dead row is written as zeros.  loc is the reference's float32 arithmetic in its order, every operation rounded
+ *   to fp32 on its own, for every row (a dead row: the same arithmetic on a zero box): column L-1 = ((y2-y1)*(x2-x1))/whp[2]
+ *   when L >= 5, columns 0..3 = x/w, y/h, columns 4, 5 = differences of the normalised coordinates when L > 5.
+ *   normalize != 0 (M3P norm_embeddings): every loc row is divided by sqrt(((s0+s1)+s2)+...), s_i = fl(x_i*x_i) -- numpy's
+ *   order for rows of 5 or 7; an all-zero row becomes NaN like the reference's -- and every live feature row becomes
+ *   x / max(||x||_2, 1e-12): sum of squares in fp64, the norm rounded to fp32 once, one fp32 division per element (within
+ *   2 * 2^-24 relative of the exact quotient).
+ *   F % 4 == 0, F <= 4096, 4 <= L <= 8; feats_packed, boxes_packed and feats 16-byte aligned.
+ * vl_collate_text: tok [n_tok] int64 token ids of all records, tok_off [B+1] int64 prefix sums (>= 2 tokens per record)
+ *   -> ids / input_mask / segment_ids [B, T] int64: [t0] + t[1:-1][:T-2] + [t_last], padded with pad_id; the mask is 1 on
+ *   the kept tokens; segment ids are zeros.  T >= 2.
+ * vl_collate_targets: labels [B, Lb] int64 in [0, C), scores [B, Lb] fp32, prior32 [C, C] fp32 (the dense table of
+ *   records.prior_table cast once; NULL: dist is written as zeros) -> target [B, C] = zeros with target[b, labels[b,l]] =
+ *   scores[b,l] (a repeated label: the highest l wins), dist[b, :] = prior32[labels[b, Lb-1], :].  C <= 4096.
+ * ------------------------------------------------------------------------------------------------------------ */
+int vl_collate_regions(const float* feats_packed, const float* boxes_packed, const int64_t* row_off, const float* whp,
+                       float* feats, float* loc, int64_t* image_mask, int64_t B, int64_t V, int64_t F, int64_t L,
+                       int64_t n_rows, int normalize, void* stream);
+int vl_collate_text(const int64_t* tok, const int64_t* tok_off, int64_t* ids, int64_t* input_mask, int64_t* segment_ids,
+                    int64_t B, int64_t T, int64_t pad_id, int64_t n_tok, void* stream);
+int vl_collate_targets(const int64_t* labels, const float* scores, const float* prior32, float* target, float* dist,
+                       int64_t B, int64_t Lb, int64_t C, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Element-wise stages of the pooler / classifier head on [M = batch, N] fp32 tensors (contiguous, ld = N).
  * Replaces: BertTextPooler's ReLU (volta/volta/encoders.py:597-608), M3P BertPooler's tanh
  * (volta/volta/m3p/m3p_transformer.py:548-560), nn.Dropout on the pooled vector (encoders.py:1238-1239) and
