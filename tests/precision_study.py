@@ -19,7 +19,12 @@ per-tensor relative L2 error of the gradients (median / max over the 215 tensors
 fp32-grade = bf16x3, the engine's choice).  `--trajectory N` additionally trains N optimizer steps with each backward
 scheme against the fp32 run (dropout 0) and prints the loss drift: the CPU rehearsal of tests/test_gpu_trajectory.py.
 
+`--slices` prints the table behind the per-slice gradient bounds of tests/grad_check.py: the oracle under
+`engine_noise_model()` -- every rounding point of the engine's step restated on the oracle side -- against the plain oracle,
+the worst of each statistic of grad_check.grad_stats over all gradient tensors and where it occurs, per shape and seed.
+
     python tests/precision_study.py --layers 12 --batch 8            # the table of DESIGN.md §2 (a few minutes on 8 cores)
+    python tests/precision_study.py --slices                         # the table of DESIGN.md §5 (two minutes on 8 cores)
 """
 import argparse
 import os
@@ -89,27 +94,88 @@ class QLinear(torch.autograd.Function):
         return dx, dw, dy2.sum(0), None, None
 
 
-class Patched(object):
-    """Context: nn.Linear (and optionally torch.matmul of the attention core) run through qmm."""
+class QMatmul(torch.autograd.Function):
+    """The two products of the attention core (Q K^T and P V) with a scheme per direction.  With bwd = "bf16" the backward
+    products read what the engine's attention backward reads: dctx as bf16 (dP = dctx V^T, dV = P^T dctx), P rounded to bf16
+    (dV), dS rounded to bf16 (dQ = dS K, dK = dS^T Q), and the bf16 halves of q, k, v."""
 
-    def __init__(self, fwd, bwd="fp32", attn=None):
-        self.fwd, self.bwd, self.attn = fwd, bwd, attn
+    @staticmethod
+    def forward(ctx, a, b, fwd, bwd):
+        ctx.save_for_backward(a, b)
+        ctx.bwd = bwd
+        return qmm(a, b, fwd)
+
+    @staticmethod
+    def backward(ctx, dy):
+        a, b = ctx.saved_tensors
+        return qmm(dy, b.transpose(-1, -2), ctx.bwd), qmm(a.transpose(-1, -2), dy, ctx.bwd), None, None
+
+
+def _bf16(x):
+    return x.to(torch.bfloat16).to(x.dtype)
+
+
+class GeluBf16Grad(torch.autograd.Function):
+    """erf-GELU whose backward is the engine's: GELU'(x) is stored as bf16 by the forward epilogue and multiplied into the bf16
+    result of the dX product behind it; the product is the (bf16) dY operand of the next backward GEMM (rounded there)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        cdf = 0.5 * (1.0 + torch.erf(x / np.sqrt(2.0)))
+        ctx.save_for_backward(_bf16(cdf + x * torch.exp(-0.5 * x * x) / np.sqrt(2.0 * np.pi)))
+        return x * cdf
+
+    @staticmethod
+    def backward(ctx, dy):
+        return _bf16(dy) * ctx.saved_tensors[0]
+
+
+class Patched(object):
+    """Context: nn.Linear (and optionally torch.matmul of the attention core) run through qmm.  attn= is one scheme for the
+    attention products in both directions (through autograd of qmm); attn_fwd= / attn_bwd= give each direction its own
+    (QMatmul); gelu_bf16 restates the bf16 GELU' of the trunk's feed-forward backward (the head computes its GELU' in fp32)."""
+
+    def __init__(self, fwd, bwd="fp32", attn=None, attn_fwd=None, attn_bwd=None, gelu_bf16=False):
+        assert not (attn and (attn_fwd or attn_bwd))
+        self.fwd, self.bwd, self.attn, self.gelu_bf16 = fwd, bwd, attn, gelu_bf16
+        self.attn_fwd, self.attn_bwd = attn_fwd, attn_bwd
 
     def __enter__(self):
         self._lin, self._mm = torch.nn.functional.linear, torch.matmul
+        self._gelu, self._head_gelu = O.gelu_erf, O._GeLU.forward
         fwd, bwd = self.fwd, self.bwd
         torch.nn.functional.linear = lambda x, w, b=None: QLinear.apply(x, w, b, fwd, bwd)
         if self.attn:
             attn = self.attn
             torch.matmul = lambda a, b: qmm(a, b, attn)
+        elif self.attn_fwd or self.attn_bwd:
+            af, ab = self.attn_fwd or "fp32", self.attn_bwd or "fp32"
+            torch.matmul = lambda a, b: QMatmul.apply(a, b, af, ab)
+        if self.gelu_bf16:
+            exact = self._gelu
+            O.gelu_erf = GeluBf16Grad.apply
+            O._GeLU.forward = lambda self_, x: exact(x)
         return self
 
     def __exit__(self, *exc):
         torch.nn.functional.linear, torch.matmul = self._lin, self._mm
+        O.gelu_erf, O._GeLU.forward = self._gelu, self._head_gelu
 
 
-def build(layers, vocab, seed, dropout0=False):
-    cfg = uc2_cfg_dict(n_layers=layers, vocab=vocab)
+def engine_noise_model():
+    """The reference-side model of the engine's rounding: forward products -- every Linear and the attention
+    core -- as 3-term split bf16; every backward product single-pass bf16, i.e. both operands rounded to bf16 where they are
+    fed.  That places the engine's backward rounding points on the oracle side:
+      * dctx (the out-projection's dX result) is fed to the attention backward as bf16       -- QMatmul.backward, dy of P V
+      * P and dS are rounded to bf16 inside the attention backward                             -- QMatmul.backward, a / dy
+      * dqkv leaves the attention backward as bf16, the LayerNorm backward's dpre16 is bf16   -- QLinear.backward, dy
+      * GELU' is saved as bf16 and multiplied into the bf16 dX result of FFN2                  -- GeluBf16Grad
+    Accumulation is fp32 on both sides.  The bounds of tests/grad_check.py come from this model, never from the engine."""
+    return Patched("bf16x3", "bf16", attn_fwd="bf16x3", attn_bwd="bf16", gelu_bf16=True)
+
+
+def build(layers, vocab, seed, dropout0=False, **width):
+    cfg = uc2_cfg_dict(n_layers=layers, vocab=vocab, **width)
     if dropout0:
         cfg.update(hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0)
     config = BertConfig.from_dict(cfg)
@@ -129,8 +195,72 @@ def run(model, batch, fwd, bwd, attn=None, grads=True):
     return logits.detach(), g
 
 
+# (name, layers, B, T, V, vocab, width): the shapes of tests/test_gpu_model.py whose noise sets the per-slice bounds
+SLICE_CASES = [("L2 B8 T20 V36", 2, 8, 20, 36, 2000, {}), ("L2 B3 T7 V9", 2, 3, 7, 9, 2000, {}),
+               ("L2 B2 T20 V100", 2, 2, 20, 100, 2000, {}), ("L2 B1 T6 V4", 2, 1, 6, 4, 2000, {}),
+               ("L12 B8 T20 V36", 12, 8, 20, 36, 2000, {}),
+               ("c1 (H128, 4 heads) L2 B4 T20 V36", 2, 4, 20, 36, 1000, dict(hidden=128, heads=4, inter=512))]
+SLICE_MARGINS = dict(scale=3.0, row=4.0, column=4.0, element=4.0)
+
+
+def noise_model_grads(model, batch):
+    """({name: gradient} of the plain fp32 oracle, the same under engine_noise_model()), eval mode: every parameter plus
+    "features.grad" [B, V, 2048] and "spatials.grad" [B, V, 7], the two input gradients the engine returns."""
+    model.eval()
+    out = []
+    for ctx in (Patched("fp32", "fp32"), engine_noise_model()):
+        model.zero_grad()
+        feats, spat = batch[0].clone().requires_grad_(True), batch[1].clone().requires_grad_(True)
+        with ctx:
+            loss, _, _ = O.forward_train(model, (feats, spat) + tuple(batch[2:]))
+            loss.backward()
+        g = {n: p.grad.detach().clone() for n, p in model.named_parameters() if p.grad is not None}
+        g["features.grad"], g["spatials.grad"] = feats.grad, spat.grad
+        out.append(g)
+    return out[0], out[1]
+
+
+def one_digit(x):
+    """x rounded to one significant digit."""
+    e = int(np.floor(np.log10(x)))
+    return round(x / 10.0 ** e) * 10.0 ** e
+
+
+def slices(args):
+    import grad_check as G
+    overall = G.Worst()
+    print("noise model (engine_noise_model) vs the plain oracle: worst of each statistic over all gradient tensors, and where")
+    print("| shape | seed | tensor | scale | row | column | element |")
+    print("|---|---|---|---|---|---|---|")
+    for name, layers, B, T, V, vocab, width in SLICE_CASES:
+        for seed in range(args.seeds):
+            model = build(layers, vocab, 40 + seed, **width)
+            batch = make_batch(B, seq_len=T, num_boxes=V, vocab_size=vocab, seed=500 + seed)
+            batch[2][0, V - 3:] = 0  # a padded image region, as in the model tests
+            gref, g = noise_model_grads(model, batch)
+            worst = G.check_grads(g, gref, check=False)
+            cells = []
+            for k in G.STATS:
+                v, n = worst[k]
+                st = G.grad_stats(g[n], gref[n])
+                at = "[%d]" % st["where"][k][0] if k in st["where"] else ""
+                cells.append("%.2e %s%s" % (v, n.replace("bert.", "").replace("encoder.", ""), at))
+                if v > overall[k][0]:
+                    overall[k] = (v, "%s, seed %d, %s%s" % (name, seed, n, at))
+            print("| %s | %d | %s |" % (name, seed, " | ".join(cells)), flush=True)
+    print("\n| statistic | worst of the noise model | where | margin | bound (one significant digit) |")
+    print("|---|---|---|---|---|")
+    for k in G.STATS:
+        v, at = overall[k]
+        if k in SLICE_MARGINS:
+            print("| %s | %.2e | %s | %.0fx | %.0e |" % (k, v, at, SLICE_MARGINS[k], one_digit(v * SLICE_MARGINS[k])))
+        else:
+            print("| %s | %.2e | %s | - | %.0e (the existing per-tensor bound) |" % (k, v, at, G.GRAD_REL_L2))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--slices", action="store_true", help="the per-slice gradient noise table of DESIGN.md section 5")
     ap.add_argument("--layers", type=int, default=12)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--vocab", type=int, default=2000)
@@ -142,6 +272,8 @@ def main():
     ap.add_argument("--traj-only", action="store_true", help="skip the single-step tables")
     args = ap.parse_args()
     torch.set_num_threads(args.threads)
+    if args.slices:
+        return slices(args)
     fwd_schemes = ["bf16", "fp16", "bf16x2_act", "bf16x2_w", "fp16x2_act", "fp16x2_w", "bf16x3", "fp16x3"]
     if args.traj_only:
         return trajectory(args)

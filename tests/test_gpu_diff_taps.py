@@ -9,9 +9,9 @@ pytestmark = pytest.mark.gpu
 
 import diff_taps_ref as R  # noqa: E402
 import dropout_masks as DM  # noqa: E402
+import grad_check as G  # noqa: E402
 from helpers import TASK_CFG, uc2_cfg_dict  # noqa: E402
-from test_gpu_dropout import GRAD_REL_L2 as DROPOUT_GRAD_REL_L2  # noqa: E402  (the bound of the dropout-on parity tests)
-from test_gpu_model import GRAD_REL_L2  # noqa: E402  (the project's bound for any gradient tensor behind the bf16 backward)
+from grad_check import GRAD_REL_L2  # noqa: E402  (the project's bound for any gradient tensor behind the bf16 backward)
 from oracle import uc2_oracle as O  # noqa: E402
 from clg_vqa_amd import ops  # noqa: E402
 from clg_vqa_amd.config import BertConfig  # noqa: E402
@@ -19,6 +19,7 @@ from clg_vqa_amd.encoders import BertForVLTasks  # noqa: E402
 from clg_vqa_amd.ops import BF16  # noqa: E402
 from clg_vqa_amd.synthetic import make_batch, seeded_state_dict  # noqa: E402
 
+DROPOUT_GRAD_REL_L2 = GRAD_REL_L2  # the dropout-on parity tests use the same bound
 DEV = "cuda"
 BASE_SEED = 0x5EED ^ 20261018
 
@@ -172,13 +173,14 @@ def _is_key_bias(n):
 
 
 def _compare(got, ref, bound, what, structurally_unused=()):
-    """Every parameter gradient + features.grad + spatials.grad of `got` against the oracle's within `bound` (per-tensor
-    relative L2).  Out of the relative check stay only tensors whose oracle gradient is EXACTLY zero -- asserted to be the
-    `structurally_unused` parameters and nothing else, and the engine's gradient there must be exactly zero too -- and the
-    key biases: no hidden state and no logit depends on them (softmax is shift invariant), so the oracle's float64 value is
-    its own rounding noise (asserted: below 1e-12 of the query bias's) and there is nothing to be relative to; they are
-    held to the absolute bound tests/test_gpu_model.py uses for them, 1e-2 of the query bias's gradient norm."""
-    worst, excluded = (0.0, None), set()
+    """Every parameter gradient + features.grad + spatials.grad of `got` against the oracle's through grad_check: within `bound`
+    per tensor (relative L2) and within its scale / row / column / element bounds (rows of features.grad and spatials.grad are
+    (sample, box)).  Tensors whose oracle gradient is EXACTLY zero -- asserted to be the `structurally_unused` parameters and
+    nothing else -- must be exactly zero in the engine too (grad_check: 0 / 0 = 0, x / 0 = inf).  The key biases: no hidden
+    state and no logit depends on them (softmax is shift invariant), so the oracle's float64 value is its own rounding noise
+    (asserted: below 1e-12 of the query bias's) and there is nothing to be relative to; they are held to the absolute bound
+    grad_check uses for them, 1e-2 of the query bias's gradient norm."""
+    excluded = set()
     tensors = dict(got["params"])
     tensors["features.grad"], tensors["spatials.grad"] = got["features"], got["spatials"]
     refs = dict(ref["params"])
@@ -187,22 +189,18 @@ def _compare(got, ref, bound, what, structurally_unused=()):
         r = refs[n].double()
         assert g is not None, "%s: %s is None" % (what, n)
         assert g.shape == r.shape and torch.isfinite(g).all(), n
-        g = g.detach().double().cpu()
         if _is_key_bias(n):
             qn = refs[n.replace("key.bias", "query.bias")].double().norm().item()
             assert r.norm().item() <= 1e-12 * max(qn, 1e-300), (n, r.norm().item(), qn)
-            assert g.norm().item() <= 1e-2 * qn, "%s: %s: %.3e against |d query.bias| %.3e" % (what, n, g.norm().item(), qn)
-            continue
-        if not r.any():
+        elif not r.any():
             excluded.add(n)
             assert not g.any(), "%s: %s: the oracle's gradient is exactly zero, the engine's is not" % (what, n)
-            continue
-        rel = (g - r).norm().item() / r.norm().item()
-        worst = max(worst, (rel, n))
-        assert rel <= bound, "%s: %s: relative L2 error %.3e (bound %.1e)" % (what, n, rel, bound)
     assert excluded == set(structurally_unused), (what, sorted(excluded ^ set(structurally_unused)))
+    stats = G.check_grads(tensors, refs, what, bounds=dict(tensor=bound))
+    worst = stats["tensor"]
     print("%s: %d tensors, worst relative L2 error %.3e at %s (bound %.1e); exactly zero: %d" % (
         what, len(tensors), worst[0], worst[1], bound, len(excluded)))
+    print("%s: %s" % (what, stats))
     return worst
 
 
@@ -267,10 +265,8 @@ def test_loss_without_the_logits_term(case):
     ref = R.oracle_tap_grads(case["oracle"], case["inputs"], E, torch.zeros_like(case["c"]), taps=(1, 4))
     for n in ("bert.encoder.layer.3.output.dense.weight", "bert.encoder.layer.0.attention_self.query.weight",
               "bert.embeddings.image_embeddings.weight", "bert.embeddings.word_embeddings.weight"):
-        g, r = dict(model.named_parameters())[n].grad.double().cpu(), ref["params"][n]
-        rel = (g - r).norm().item() / r.norm().item()
-        print("taps only: %s relative L2 error %.3e" % (n, rel))
-        assert rel <= GRAD_REL_L2, (n, rel)
+        st = G.grad_check("taps only: " + n, dict(model.named_parameters())[n].grad, ref["params"][n])
+        print("taps only: %s relative L2 error %.3e; %s" % (n, st["tensor"], G.fmt(st)))
     assert model.bert.t_pooler.dense.weight.grad is None  # nothing reached the head
 
 
@@ -315,9 +311,8 @@ def test_token_saliency(case):
     pad = case["inputs"][4][1] == 0
     assert pad.sum() == 2 and ref[1][pad].abs().sum() > 0
     for what, g, r in (("all token positions", sal, ref), ("padded positions", sal[1][pad], ref[1][pad])):
-        rel = (g - r).norm().item() / r.norm().item()
-        print("token saliency, %s: relative L2 error %.3e (bound %.1e)" % (what, rel, GRAD_REL_L2))
-        assert rel <= GRAD_REL_L2, (what, rel)
+        st = G.grad_check("token saliency, " + what, g, r)  # rows = (sample, token)
+        print("token saliency, %s: relative L2 error %.3e (bound %.1e); %s" % (what, st["tensor"], GRAD_REL_L2, G.fmt(st)))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -9,9 +9,10 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import grad_check as G  # noqa: E402
 import input_grads_ref as R  # noqa: E402
 from helpers import TASK_CFG, uc2_cfg_dict  # noqa: E402
-from test_gpu_model import GRAD_REL_L2  # noqa: E402  (the project's bound for any gradient tensor behind the bf16 backward)
+from grad_check import GRAD_REL_L2  # noqa: E402  (the project's bound for any gradient tensor behind the bf16 backward)
 from oracle import m3p_oracle as Mo  # noqa: E402
 from oracle import uc2_oracle as O  # noqa: E402
 from clg_vqa_amd import _lib, ops, task_utils  # noqa: E402
@@ -145,9 +146,9 @@ def _check_input_grad(got, like, ref, what):
     assert got is not None, "%s: .grad is None" % what
     assert got.shape == like.shape and got.dtype == torch.float32 and got.is_cuda, what
     assert torch.isfinite(got).all(), what
-    rel = R.rel_l2(got, ref)
-    print("%s: relative L2 error %.3e (bound %.1e)" % (what, rel, GRAD_REL_L2))
-    assert rel <= GRAD_REL_L2, "%s: relative L2 error %.3e" % (what, rel)
+    st = G.grad_check(what, got, ref)  # [B, V, F] viewed as [B V, F]: rows = (sample, box)
+    rel = st["tensor"]
+    print("%s: relative L2 error %.3e (bound %.1e); %s" % (what, rel, GRAD_REL_L2, G.fmt(st)))
     return rel
 
 

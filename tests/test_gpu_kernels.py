@@ -8,6 +8,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import attn_bwd_ref as AR  # noqa: E402
 from clg_vqa_amd import ops  # noqa: E402
 from clg_vqa_amd.ops import BF16, EPI_BF16, EPI_DGELU_BF16, EPI_F32, EPI_GELU_SPLIT, EPI_SPLIT  # noqa: E402
 
@@ -679,6 +680,8 @@ def test_attention2_forward_backward(B, T, V):
     err = (dqkv.double() - g).abs().max().item()
     print("attn2 bwd B=%d S=%d: rel-L2 %.3e, max abs %.3e (grad max %.3e)" % (B, S, rel, err, g.abs().max().item()))
     assert rel <= 2e-2 and err <= 3e-2 * g.abs().max().item()  # P / dS are rounded to bf16 inside (2^-9 relative each)
+    # per (q / k / v, head) block and per sequence row of a block, against the restatement with the kernel's lse / P / dS points
+    AR.check_blocks("attn2 bwd B=%d S=%d" % (B, S), dqkv, hi, lo, addmask.view(B, S), d16, B, S, nh, 64)
 
 
 @pytest.mark.parametrize("B,S", [(3, 56), (2, 120), (1, 10), (2, 140), (1, 156)])  # (4 / 8 / 9 / 10 key-tile instances)
@@ -711,6 +714,42 @@ def test_attention2_head_dim_32(B, S):
     ops.attn2_bwd(hi, addmask, d16, lse, dqkv, B, S, nh, dh, 0.0, 1)
     rel = (dqkv.double() - qh.grad).norm().item() / qh.grad.norm().item()
     assert rel <= 2e-2, rel
+    AR.check_blocks("attn2 bwd dh=32 B=%d S=%d" % (B, S), dqkv, hi, lo, addmask.view(B, S), d16, B, S, nh, dh)
+
+
+@pytest.mark.parametrize("B,S,dh", AR.EDGE_CASES)
+def test_attention2_dispatch_edges(B, S, dh):
+    """S on both sides of the thresholds at which the library picks another kernel instance (4 / 5 / 8 / 9 / 10 key tiles at
+    S <= 64 / 80 / 128 / 144 / 160): 64, 65, 81, 128, 129, 144, 145, head dim 64 and (65, 129) 32, B <= 2, a padded key tail in the
+    LAST sample and masked region positions in the middle of sample 0's sequence.
+    Forward against fp64 at the (hi + lo) operands (3e-5); backward as a whole against autograd (2e-2) and per block / per row
+    against the restatement with the kernel's lse / P / dS points (tests/attn_bwd_ref.py)."""
+    nh = 4
+    H = nh * dh
+    qkv, dO, addmask2 = AR.case_inputs(B, S, nh, dh, 300 + S + dh, "edge", device=DEV)
+    assert (addmask2[-1, S - 7:] < 0).all() and (addmask2[0, S // 2 - 3:S // 2 + 2] < 0).all()
+    assert B == 1 or addmask2[0, S - 1] == 0
+    hi, lo = _split(qkv)
+    addmask = addmask2.reshape(-1).contiguous()
+    ctx_hi = torch.full((B * S, H), float("nan"), dtype=BF16, device=DEV)
+    ctx_lo = torch.full_like(ctx_hi, float("nan"))
+    lse = torch.empty(B * nh * S, device=DEV)
+    ops.attn2_fwd(hi, lo, addmask, ctx_hi, ctx_lo, lse, B, S, nh, dh, 0.0, 1)
+    x = (hi.double() + lo.double()).view(B, S, 3, nh, dh)
+    q, k, v = x[:, :, 0].permute(0, 2, 1, 3), x[:, :, 1].permute(0, 2, 1, 3), x[:, :, 2].permute(0, 2, 1, 3)
+    sc = q @ k.transpose(-1, -2) / math.sqrt(dh) + addmask2.double().view(B, 1, 1, S)
+    ref = (torch.softmax(sc, -1) @ v).permute(0, 2, 1, 3).reshape(B * S, H)
+    got = ctx_hi.double() + ctx_lo.double()
+    assert (got - ref).abs().max().item() < 3e-5 * max(1.0, ref.abs().max().item())
+    d16 = dO.to(BF16)
+    dqkv = torch.full((B * S, 3 * H), float("nan"), dtype=BF16, device=DEV)
+    ops.attn2_bwd(hi, addmask, d16, lse, dqkv, B, S, nh, dh, 0.0, 1)
+    assert torch.isfinite(dqkv.float()).all()
+    g = AR.attn_bwd_restated(hi.double(), addmask2, d16.double(), B, S, nh, dh, rounded=False)  # = fp64 autograd
+    rel = (dqkv.double() - g).norm().item() / g.norm().item()
+    print("attn2 edge B=%d S=%d dh=%d: bwd rel-L2 %.3e" % (B, S, dh, rel))
+    assert rel <= 2e-2, rel
+    AR.check_blocks("attn2 edge B=%d S=%d dh=%d" % (B, S, dh), dqkv, hi, lo, addmask2, d16, B, S, nh, dh)
 
 
 @pytest.mark.parametrize("H", [128])
